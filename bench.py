@@ -7,7 +7,7 @@ scenes (geometry of generateSyntheticScene.m, sigma = 1 px), 200
 correspondences each; one "step" = linearTFT + R_t_from_TFT for the whole batch
 (LinearTFTPoseEstimation without the Reconst output), inputs resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver as `python -m torch.distributed.run ...`: one
 process per GPU, every rank owns a batch of its own (weak scaling, independent
 triplets, no collective on the data path) and the fixed-size result records are
@@ -18,19 +18,30 @@ HIP streams (default 2, one library context per stream, result records
 double-buffered): 10 000 triplets are 2 500 wavefronts of four triplets on
 2 048 wavefront slots, and the next batch's wavefronts fill the slots the
 previous batch's tail leaves idle.  Every step still runs whole inside the
-timed region.  What the line reports, so that it closes on itself:
-  * `value`, `ms_per_step`: K steps between barrier + synchronize, repeated
-    `--reps` times, the MEDIAN repetition (all of them listed);
-  * `in_flight`: batches that may be resident at once (= streams);
+timed region.  A plain run sets up, warms up (W steps, then more until the
+warm-up has lasted 0.25 s), times K steps once, writes the last step's outputs
+if asked to, and prints its line:
+  * `value`, `ms_per_step`: K steps between barrier + synchronize (with
+    `--reps R`, that region repeated R times and the MEDIAN repetition
+    reported, all of them listed);
+  * `in_flight`: batches that may be resident at once (= streams).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's batch)
+as DIR/R_t_2.npy (B,3,4), R_t_3.npy (B,3,4), T.npy (B,3,3,3) and status.npy
+(B,), float64, in the shapes of api.Context.pose_batch.  The inputs are seeded,
+so runs with the same arguments see the same batch.
+`--full` adds everything else the line has carried (default `--reps` 7):
   * `roofline.kernel_ms` / `achieved` / `frac`: one call's launches with the
     GPU TO ITSELF (one stream, HIP events on that stream around every call,
     nothing else queued) -- the figure `rocprofv3 --kernel-trace --stats` of
     `bench.py --streams 1` reproduces (profiles/);
   * `overlap_factor` = kernel_ms / ms_per_step (<= in_flight): how much of a
     launch is hidden behind its neighbour; kernel_ms * steps / in_flight <=
-    ms_per_step * steps can be checked from the line alone.
+    ms_per_step * steps can be checked from the line alone;
+  * `single_stream`, `fp64_valu`, the other methods (`secondary`), the N sweep,
+    config 4 and the CPU baselines (`--no-secondary`, `--no-cpu-baseline`
+    leave them out).
 
-Rank 0 prints ONE JSON line (metric, value, roofline, cpu_baseline, ...).
+Rank 0 prints ONE JSON line (metric, value, ms_per_step, ...).
 """
 import argparse
 import json
@@ -107,6 +118,27 @@ def cpu_baseline_reference(N):
         return {"error": repr(ex)}
 
 
+WARMUP_MIN_S = 0.25
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, rec, status, B):
+    """One step's outputs as a caller of api.Context.pose_batch receives them: rec = the step's 51*B-double record block
+    [R_t_2 (B x 12) | R_t_3 (B x 12) | T (B x 27)], status (B,) int32.  float64 .npy files; past DUMP_MAX_BYTES a fixed,
+    seeded sample of triplets (its indices in sample_index.npy)."""
+    rec = rec.cpu().numpy()
+    out = {"R_t_2": rec[:12 * B].reshape(B, 4, 3).transpose(0, 2, 1), "R_t_3": rec[12 * B:24 * B].reshape(B, 4, 3).transpose(0, 2, 1),
+           "T": rec[24 * B:51 * B].reshape(B, 3, 3, 3).transpose(0, 3, 2, 1), "status": status.cpu().numpy().astype(np.float64)}
+    keep = (DUMP_MAX_BYTES - 4096) // (8 * 53)              # 51 record doubles + status + sample index per triplet; .npy headers
+    if B > keep:
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        out = {k: v[idx] for k, v in out.items()}
+        out["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -118,7 +150,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary blocks (other methods, N sweep, config 4; 1 GPU, rank 0)")
     ap.add_argument("--streams", type=int, default=2, help="HIP streams the steps alternate between (1 = strictly one batch at a time)")
-    ap.add_argument("--reps", type=int, default=7, help="repetitions of the timed K-step region; the median repetition is reported")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region; the median repetition is reported (default 1, 7 with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-launch and one-stream roofline figures, other methods, "
+                         "N sweep, config 4, CPU baselines")
     ap.add_argument("--force-process-group", action="store_true",
                     help="TEST SEAM (tests/test_gpu_process_group.py): at WORLD_SIZE = 1 still create the nccl (= RCCL) process group, a clique of one, and "
                          "run the overlapped all-gather of every step through it; the line then carries `process_group_check`")
@@ -126,6 +162,8 @@ def main():
                     help="TEST SEAM (tests/test_bench_flow_gloo.py): CPU tensors + gloo, the HIP launch replaced by a tagged fill -- everything around it "
                          "(rendezvous, rank-0 build + barrier, step / gather pipeline, weak-scaling accounting, the JSON line) runs as on the GPUs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -216,10 +254,27 @@ def main():
             c.synchronize()
         dsync()
 
-    for k in range(args.warmup):
-        step(k)
-    drain()
-    sync_all()
+    def warm(k0, n):
+        for k in range(k0, k0 + n):
+            step(k)
+        drain()
+        sync_all()
+        return k0 + n
+
+    def warm_seconds(t0):                                  # the least over ranks: every rank then runs the same steps (each one gathers)
+        t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        return float(t.item())
+
+    # --warmup steps, then more in doubling rounds until the device has been busy for WARMUP_MIN_S: after a few milliseconds of steps the
+    # first timed region still ran ~2 ms longer than every region after it
+    t0 = time.perf_counter()
+    n_warm = warm(0, args.warmup)
+    n = max(1, args.warmup)
+    while warm_seconds(t0) < WARMUP_MIN_S:
+        n_warm = warm(n_warm, n)
+        n *= 2
 
     def timed_region():
         """EXACTLY --steps steps between barrier + synchronize on both sides; returns the seconds (max over ranks)."""
@@ -241,33 +296,39 @@ def main():
             dt = float(t.item())
         return dt
 
-    # the region is a few milliseconds of wall clock: it is repeated and the MEDIAN repetition is the one reported (every repetition listed)
-    reps = max(1, args.reps)
+    # --full: the region is a few milliseconds of wall clock, so it is repeated and the MEDIAN repetition is the one reported (every repetition listed)
+    reps = max(1, args.reps if args.reps is not None else (7 if args.full else 1))
     rep_s = [timed_region() for _ in range(reps)]
     elapsed = float(np.median(rep_s))
-    # per-launch HIP events of one more, UNTIMED repetition of the same loop: how long a launch lasts while its neighbour shares the GPU
-    events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if not stub else [None] * args.steps
-    timing["events"] = events
-    for k in range(args.steps):
-        step(k)
-    drain()
-    timing["events"] = None
-    sync_all()
-    if world > 1:
-        dist.barrier()
-    dsync()
+    if args.dump_outputs and rank == 0:                     # before anything below reuses the record buffers
+        last = args.steps - 1
+        dump_outputs(args.dump_outputs, pipe.recs[last % pipe.nbuf], statuses[last % S], B)
+    if args.full:
+        # per-launch HIP events of one more, UNTIMED repetition of the same loop: how long a launch lasts while its neighbour shares the GPU
+        events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if not stub else [None] * args.steps
+        timing["events"] = events
+        for k in range(args.steps):
+            step(k)
+        drain()
+        timing["events"] = None
+        sync_all()
+        if world > 1:
+            dist.barrier()
+        dsync()
     n_bad = sum(int((st_ != 0).sum().item()) for st_ in statuses)
     pg_last, pg_check = None, None
-    if use_pg and not stub and rank == 0:                   # rank 0's own records as the last step's all-gather delivered them
+    if args.full and use_pg and not stub and rank == 0:     # rank 0's own records as the last step's all-gather delivered them
         pg_last = pipe.gathered[(args.steps - 1) % pipe.nbuf][rank].clone()
     for c in ctxs:                                          # the secondary blocks below run on the main stream, one call at a time
         c.set_stream(stream.cuda_stream)
-    if stub:
+    if not args.full:
+        inflight_ms = None
+    elif stub:
         inflight_ms = np.array(stub_ms) if stub_ms else np.array([float("nan")])
     else:
         inflight_ms = np.array([a.elapsed_time(b) for a, b in events]) if events else np.array([float("nan")])
     gather_check = None
-    if stub and world > 1:                                  # every rank's records of the last step arrived complete and in rank order
+    if args.full and stub and world > 1:                    # every rank's records of the last step arrived complete and in rank order
         kl = args.steps - 1
         g_ = pipe.gathered[kl % pipe.nbuf]
         n_ = g_.shape[1]
@@ -290,7 +351,7 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     single, iso_ms = None, None
-    if rank == 0 and not stub:
+    if args.full and rank == 0 and not stub:
         # the same call with the GPU to itself: one stream, nothing else queued, HIP events on that stream around every call (both launches of a
         # call inside the pair)
         r0 = pipe.recs[0]
@@ -315,7 +376,7 @@ def main():
             torch.cuda.synchronize(dev)
             pg_check = {"forced": args.force_process_group, "backend": dist.get_backend(), "world": world, "streams": S,
                         "gathered_equals_single_stream": bool(torch.equal(pg_last, r0)), "records": int(r0.numel())}
-    if rank == 0 and world == 1 and not args.no_secondary and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not stub:
         it32 = torch.zeros(B, dtype=torch.int32, device=dev)
         r = pipe.recs[0]
         for name in ("LinearFPoseEstimation", "OptimFPoseEstimation", "ResslTFTPoseEstimation", "NordbergTFTPoseEstimation",
@@ -369,12 +430,9 @@ def main():
         total = world * B * args.steps
         value = total / elapsed
         ms_per_step = 1e3 * elapsed / args.steps
-        alg = algorithmic_bytes_per_triplet(N) * B
-        kern_ms = float(iso_ms.mean()) if iso_ms is not None else float(inflight_ms.mean())
-        achieved = alg / (kern_ms * 1e-3) / 1e9
         traffic, valu = None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc):
+        if args.full and os.path.exists(pmc):
             try:
                 pj = json.load(open(pmc))
                 traffic = pj.get("hbm_bytes_per_launch")
@@ -405,9 +463,8 @@ def main():
             "value": value, "unit": "triplet-hypotheses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
-            # batches that may be resident on a GPU at once (consecutive steps alternate between that many streams), and how much of a launch
-            # is hidden behind its neighbour: kernel_ms (GPU to itself) / ms_per_step; kernel_ms * steps / in_flight <= ms_per_step * steps
-            "in_flight": S, "overlap_factor": kern_ms / ms_per_step,
+            # batches that may be resident on a GPU at once (consecutive steps alternate between that many streams)
+            "in_flight": S,
             "repetitions": {"n": reps, "reported": "median", "ms_per_step_each": [1e3 * t_ / args.steps for t_ in rep_s],
                             "timed_region_ms_each": [1e3 * t_ for t_ in rep_s]},
             "config": {"workload": "configs[1]: batch of %d synthetic triplets x %d correspondences, sigma=1px, "
@@ -415,20 +472,27 @@ def main():
                        "batch_per_gpu": B, "correspondences": N,
                        "streams": "%d (consecutive batches alternate between streams and may overlap)" % S if S > 1 else "1",
                        "gather": ("%s all_gather of 408-B result records, overlapped" % ("gloo (stub)" if stub else "RCCL")) if world > 1 else "none (1 GPU)",
-                       "failed_triplets": n_bad},
+                       "failed_triplets": n_bad, "warmup_steps_run": n_warm},
+        }
+        if args.full:
+            alg = algorithmic_bytes_per_triplet(N) * B
+            kern_ms = float(iso_ms.mean()) if iso_ms is not None else float(inflight_ms.mean())
+            achieved = alg / (kern_ms * 1e-3) / 1e9
+            # how much of a launch is hidden behind its neighbour: kernel_ms (GPU to itself) / ms_per_step; kernel_ms * steps / in_flight <= ms_per_step * steps
+            out["overlap_factor"] = kern_ms / ms_per_step
             # ONE launch, ONE duration: the call with the GPU to itself (see the docstring); `in_flight_launch_ms` is the same call's HIP-event
             # duration while its neighbour on the other stream shares the GPU (longer: not the kernel's own time, reported for the record only)
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "kernel": "k_linear_tft_pose_rows", "kernel_ms": kern_ms,
-                         "kernel_ms_how": "HIP events on the launch stream around every call (k_linear_tft_pose_rows + the exact kernel's status scan), "
-                                          "one stream, device idle before every call, mean of %d calls" % (len(iso_ms) if iso_ms is not None else 0),
-                         "kernel_ms_min": float(iso_ms.min()) if iso_ms is not None else None,
-                         "kernel_ms_median": float(np.median(iso_ms)) if iso_ms is not None else None,
-                         "in_flight_launch_ms": float(inflight_ms.mean()),
-                         "algorithmic_bytes_per_launch": alg,
-                         # the rate the device delivers with `in_flight` batches resident: algorithmic bytes of a step over ms_per_step
-                         "delivered": {"achieved": alg / (ms_per_step * 1e-3) / 1e9, "frac": alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, "unit": "GB/s per GPU"}},
-        }
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic, "kernel": "k_linear_tft_pose_rows", "kernel_ms": kern_ms,
+                               "kernel_ms_how": "HIP events on the launch stream around every call (k_linear_tft_pose_rows + the exact kernel's status scan), "
+                                                "one stream, device idle before every call, mean of %d calls" % (len(iso_ms) if iso_ms is not None else 0),
+                               "kernel_ms_min": float(iso_ms.min()) if iso_ms is not None else None,
+                               "kernel_ms_median": float(np.median(iso_ms)) if iso_ms is not None else None,
+                               "in_flight_launch_ms": float(inflight_ms.mean()),
+                               "algorithmic_bytes_per_launch": alg,
+                               # the rate the device delivers with `in_flight` batches resident: algorithmic bytes of a step over ms_per_step
+                               "delivered": {"achieved": alg / (ms_per_step * 1e-3) / 1e9, "frac": alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                             "unit": "GB/s per GPU"}}
         if single:
             out["single_stream"] = single
         if valu:
@@ -443,7 +507,7 @@ def main():
             out["process_group_check"] = pg_check
         if stub:
             out["stub"] = {"compute": "tagged fill on CPU tensors (test seam, not a measurement)", "gather_check": gather_check}
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             sample = args.cpu_sample or max(1024, 40 * (os.cpu_count() or 1))   # ~10 s of wall time on the box's host cores
             out["cpu_baseline"] = cpu_baseline(C, CalM, min(sample, B))
             out["cpu_baseline_lapack"] = cpu_baseline_lapack(C, CalM)

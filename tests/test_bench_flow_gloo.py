@@ -9,6 +9,8 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -28,7 +30,8 @@ def _torchrun(script, *args, nproc=2):
 
 def test_bench_main_flow_at_world_size_two():
     B, K, W = 65, 4, 1
-    d = _torchrun("bench.py", "--gpus", "2", "--steps", str(K), "--warmup", str(W), "--batch", str(B), "--ncorr", "20", "--stub-compute")
+    d = _torchrun("bench.py", "--gpus", "2", "--steps", str(K), "--warmup", str(W), "--batch", str(B), "--ncorr", "20", "--stub-compute",
+                  "--full")
     assert d["n_gpus"] == 2 and d["steps"] == K and d["warmup"] == W and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["metric"].startswith("triplet-hypotheses/sec") and d["unit"] == "triplet-hypotheses/s" and d["dtype"] == "f64"
     assert d["stub"]["gather_check"] is True             # both ranks' records of the last step, complete and in rank order
@@ -45,6 +48,24 @@ def test_bench_single_process_stub_has_no_collective():
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["gather"] == "none (1 GPU)" and d["stub"]["gather_check"] is None
+
+
+def test_bench_plain_run_times_steps_once_and_dumps_the_last_step(tmp_path):
+    """No --full: exactly --steps timed steps, once, and none of the --full blocks; --dump-outputs writes the last step's records in
+    api.Context.pose_batch's shapes (the stub's tagged fill of step k is k + 1e-9 * position in the record block)."""
+    B, K = 32, 3
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-compute", "--steps", str(K), "--warmup", "1", "--batch", str(B),
+                        "--ncorr", "12", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == K and d["repetitions"]["n"] == 1 and abs(d["value"] * d["ms_per_step"] * 1e-3 - B) < 1e-6 * B
+    assert d["unit"] == "triplet-hypotheses/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert not {"roofline", "overlap_factor", "single_stream", "cpu_baseline"} & set(d)
+    got = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in ("R_t_2", "R_t_3", "T", "status")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["R_t_2"].shape == got["R_t_3"].shape == (B, 3, 4) and got["T"].shape == (B, 3, 3, 3) and got["status"].shape == (B,)
+    rec = np.concatenate([got["R_t_2"].transpose(0, 2, 1).ravel(), got["R_t_3"].transpose(0, 2, 1).ravel(), got["T"].transpose(0, 3, 2, 1).ravel()])
+    assert np.abs(rec - ((K - 1) + np.arange(51 * B) * 1e-9)).max() < 1e-12 and not got["status"].any()
 
 
 def test_config4_shard_and_count_gather_at_uneven_size():

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_pipeline_through_a_clique_of_one_rccl_group(streams):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--streams", str(streams), "--steps", "8", "--warmup", "2", "--reps", "2",
-                        "--batch", "4099", "--ncorr", "60", "--force-process-group", "--no-secondary", "--no-cpu-baseline"],
+                        "--batch", "4099", "--ncorr", "60", "--force-process-group", "--no-secondary", "--no-cpu-baseline",
+                        "--full"],
                        capture_output=True, text=True, timeout=560, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

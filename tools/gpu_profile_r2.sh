@@ -6,7 +6,7 @@ WHAT=${1:-headline}
 OUT=$R/gpurun_out/prof_r2_$WHAT; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 case $WHAT in
-  headline) CMD="python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 3"; export PROFILE_KERNEL=k_linear_tft_pose;;
+  headline) CMD="python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 3"; export PROFILE_KERNEL=k_linear_tft_pose;;
   ressl)    CMD="python3 $R/tools/bench_one.py ResslTFTPoseEstimation 10"; export PROFILE_KERNEL="k_gh_block";;
   nordberg) CMD="python3 $R/tools/bench_one.py NordbergTFTPoseEstimation 10"; export PROFILE_KERNEL="k_gh_block";;
   faugpapa) CMD="python3 $R/tools/bench_one.py FaugPapaTFTPoseEstimation 6"; export PROFILE_KERNEL="k_gh_block";;

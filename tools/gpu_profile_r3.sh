@@ -24,7 +24,7 @@ PY
 ALG=$((10000 * (48 * 200 + 216 + 216 + 192)))
 for T in ${@:-headline ressl nordberg faugpapa pi picol linearf optimf config4tft config4f}; do
   case $T in
-    headline)   run_one headline "python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 3" "k_linear_tft_pose<false>" 10000 $ALG 2;;
+    headline)   run_one headline "python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 3" "k_linear_tft_pose<false>" 10000 $ALG 2;;
     ressl)      run_one ressl "python3 $R/tools/bench_one.py ResslTFTPoseEstimation 8" "k_gh_block" 10000 $ALG 2;;
     nordberg)   run_one nordberg "python3 $R/tools/bench_one.py NordbergTFTPoseEstimation 8" "k_gh_block" 10000 $ALG 3;;
     faugpapa)   run_one faugpapa "python3 $R/tools/bench_one.py FaugPapaTFTPoseEstimation 6" "k_fp_block" 10000 $ALG 3;;

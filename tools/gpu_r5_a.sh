@@ -5,7 +5,7 @@ O=$R/gpurun_out/r5; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -q -x --timeout 900 > $O/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $O/pytest_gpu.log
 tail -5 $O/pytest_gpu.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench.json") if l.startswith("{")][-1])
@@ -16,6 +16,6 @@ PY
 ./tools/micro/fp64_issue > $O/r5_fp64_issue.txt 2>&1; cat $O/r5_fp64_issue.txt
 ./tools/micro/dpp_fmac > $O/r5_dpp_fmac.txt 2>&1; tail -8 $O/r5_dpp_fmac.txt
 ( cd /tmp && export TMPDIR=/tmp
-  rm -rf $R/gpurun_out/prof_r5_overlap
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_r5_overlap -- python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 3 > $O/overlap_trace.log 2>&1 )
-python tools/overlap_trace.py $R/gpurun_out/prof_r5_overlap k_linear_tft_pose_rows $O/r5_headline
+  rm -rf $O/prof_r5_overlap
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r5_overlap -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 3 > $O/overlap_trace.log 2>&1 )
+python tools/overlap_trace.py $O/prof_r5_overlap k_linear_tft_pose_rows $O/r5_headline

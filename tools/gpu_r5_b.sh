@@ -8,7 +8,7 @@ timeout 300 python tools/ab_pre.py 10000 8 ResslTFTPoseEstimation 60 200 > $O/r5
 ./tools/micro/fp64_issue > $O/r5_fp64_issue.txt 2>&1; cat $O/r5_fp64_issue.txt
 timeout 1500 python -m pytest tests/test_gpu_rows.py tests/test_gpu_dropin_single.py tests/test_gpu_parity.py tests/test_gpu_gh_noise.py -m gpu -q -x --timeout 900 > $O/pytest_gpu_b.log 2>&1; echo "pytest rc $?" >> $O/pytest_gpu_b.log
 tail -5 $O/pytest_gpu_b.log
-timeout 600 python bench.py --no-cpu-baseline > $O/bench_b.json 2> $O/bench_b.err; echo "bench rc $?"
+timeout 600 python bench.py --full --no-cpu-baseline > $O/bench_b.json 2> $O/bench_b.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench_b.json") if l.startswith("{")][-1])
