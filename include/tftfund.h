@@ -21,6 +21,10 @@
  *   reconst  B x (3 x N) or NULL                                   (Reconst, 3xN)
  *   iter     B int32 or NULL  (0 for the linear methods, GH iterations otherwise)
  *   status   B int32 or NULL  (replaces MATLAB exceptions, see TFF_ST_*)
+ * Ragged batches (tff_pose_batch_ragged_*, tff_repr_error_ragged_dev): triplets with different correspondence counts, packed:
+ *   offsets  B + 1 int64; triplet b owns correspondences offsets[b] .. offsets[b+1]-1, n_b = offsets[b+1] - offsets[b]
+ *   corresp  correspondence n of triplet b = [x1 y1 x2 y2 x3 y3] at corresp[(offsets[b] + n)*6]
+ *   reconst  3 doubles per correspondence at reconst[(offsets[b] + n)*3] or NULL;  calm, Rt2, Rt3, T, iter, status as above
  *
  * Every function returns 0 on success or a negative code (-hipError_t for HIP
  * failures, TFF_E_* otherwise); tff_last_error() gives a thread-local message.
@@ -56,6 +60,7 @@ typedef struct tff_ctx tff_ctx;
 #define TFF_ST_NO_POSE 3    /* no candidate with score >= 0: R_f unassigned in R_t_from_TFT.m:91-104 */
 #define TFF_ST_NO_PARAM 5   /* PiColPoseEstimation.m:84-89: error('The minimal param could not be found') */
 #define TFF_ST_RANK 4       /* Nordberg: P2(:,1:3) or P3(:,1:3) of rank < 2 (NordbergTFT...m:58,60 would fail: null() returns two columns) */
+#define TFF_ST_BAD_OFFSETS 6 /* ragged calls (_dev): offsets[b+1] < offsets[b], offsets[b] < 0, or n_b > n_max -- NaN poses for that item only */
 
 /* error codes (besides -hipError_t) */
 #define TFF_E_INVALID (-10001)
@@ -322,6 +327,27 @@ int tff_pose_batch_host_multi(tff_multi* m, int32_t method, const double* corres
  * device = [Rt2 (chunk x 12) | Rt3 (chunk x 12) | T (chunk x 27)] of shard r.  status[g] (or status == NULL): G * chunk int32. */
 int tff_pose_batch_dev_multi(tff_multi* m, int32_t method, const double* const* corresp, const double* const* calm,
                              int64_t calm_stride, int64_t B, int32_t N, double* const* records, int32_t* const* status);
+
+/* ---- ragged batches: one call for triplets with different correspondence counts (layout at the top) -------------------------------
+ * Each triplet's outputs are bit-identical to those of the fixed-N entry point of the method called on that triplet alone, under the same
+ * context options: triplet b takes the kernels the fixed-N call takes for n_b (TFF_ST_TOO_FEW below 7 / 8 correspondences, the exact tiers
+ * below TFF_OPT_EXACT_BELOW or with TFF_OPT_SOLVER = 1, the exact fix-up of what the fast tiers flag), and writes what that call writes,
+ * its Reconst range included.  Methods: TFF_METHOD_LINEAR_TFT and TFF_METHOD_LINEAR_F (others: TFF_E_INVALID).  TFF_OPT_PRE is ignored
+ * (the moments come from the row kernels' own passes, the default); TFF_OPT_ROWS = 0 and TFF_OPT_KERNEL = 1 give TFF_E_INVALID.
+ * _dev: device pointers, offsets included; n_max (host) bounds every n_b (at most 2^24) and sizes the plan's workspace: the plan keeps
+ * three int32 per n in 0 .. n_max and scans them in one workgroup, so its cost grows with n_max, not with B (n_max = 2^24: ~200 MB and a
+ * scan of 16 M buckets per call) -- pass a bound close to the largest n_b; an item that breaks
+ * it, or whose offsets decrease or are negative, gets TFF_ST_BAD_OFFSETS and NaN poses while its neighbours are unaffected.  No host
+ * synchronisation and no device-to-host copy: after a warm-up call with the same method, B and n_max at least as large, a call can be
+ * captured in a hipGraph.  B = 0 returns 0; at most 2^28 - 1 triplets per call. */
+int tff_pose_batch_ragged_dev(tff_ctx* ctx, int32_t method, const double* corresp, const int64_t* offsets, int32_t n_max,
+                              const double* calm, int64_t calm_stride, int64_t B, double* Rt2, double* Rt3, double* T,
+                              double* reconst, int32_t* iter, int32_t* status);
+/* host pointers; n_max is computed; decreasing or negative offsets give TFF_E_INVALID before any work.  The packed range
+ * offsets[0] .. offsets[B] of corresp is read and the same range of reconst written. */
+int tff_pose_batch_ragged_host(tff_ctx* ctx, int32_t method, const double* corresp, const int64_t* offsets, const double* calm,
+                               int64_t calm_stride, int64_t B, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter,
+                               int32_t* status);
 
 #ifdef __cplusplus
 }

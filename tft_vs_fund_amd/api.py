@@ -42,6 +42,7 @@ TFF_OPT_PRE = 10
 DEBUG_STRIDE = 128
 
 ST_OK, ST_TOO_FEW, ST_NONFINITE, ST_NO_POSE, ST_RANK, ST_NO_PARAM = 0, 1, 2, 3, 4, 5
+ST_BAD_OFFSETS = 6
 
 _c_dp = ctypes.c_void_p
 _POSE_SIG = [ctypes.c_void_p, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -108,6 +109,8 @@ def load_library(path=None):
             "tff_multi_create": [ctypes.POINTER(ctypes.c_void_p), V, I32],
             "tff_pose_batch_host_multi": [V, I32, V, V, I64, I64, I32, V, V, V, V, V, V],
             "tff_pose_batch_dev_multi": [V, I32, V, V, I64, I64, I32, V, V],
+            "tff_pose_batch_ragged_dev": [V, I32, V, V, I32, V, I64, I64, V, V, V, V, V, V],
+            "tff_pose_batch_ragged_host": [V, I32, V, V, V, I64, I64, V, V, V, V, V, V],
         }
         for name, sig in protos.items():
             fn = getattr(lib, name)
@@ -149,11 +152,47 @@ EXPORTED_SYMBOLS = [
     "tff_triangulate_batch_dev", "tff_repr_error_batch_dev", "tff_inlier_count_batch_dev", "tff_transform_tft_batch_dev",
     "tff_rt_from_tft_batch_dev", "tff_linear_tft_batch_dev", "tff_linear_f_batch_dev", "tff_bundle_adjust_batch_dev", "tff_bundle_adjust_batch_host", "tff_bundle_adjust_views_batch_dev", "tff_bundle_adjust_views_batch_host", "tff_linear_tft_pose_sampled_dev", "tff_linear_f_pose_sampled_dev",
     "tff_multi_create", "tff_multi_destroy", "tff_multi_size", "tff_multi_ctx", "tff_multi_shard", "tff_pose_batch_host_multi", "tff_pose_batch_dev_multi",
+    "tff_pose_batch_ragged_dev", "tff_pose_batch_ragged_host",
 ]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
               "PiPoseEstimation": 4, "PiColPoseEstimation": 5, "LinearFPoseEstimation": 6, "OptimFPoseEstimation": 7}
+
+
+# methods a ragged call (Context.pose_batch_ragged) supports
+RAGGED_METHODS = ("LinearTFTPoseEstimation", "LinearFPoseEstimation")
+
+
+def pack_ragged(items):
+    """A list of (n_b, 6) correspondence arrays (n_b may differ, and be 0) -> (corresp (sum n_b, 6) float64, offsets (B + 1,) int64):
+    the packed layout of the ragged entry points, triplet b = corresp[offsets[b]:offsets[b + 1]]."""
+    arrs = []
+    for k, a in enumerate(items):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or (a.shape[1] != 6 and a.size):
+            raise ValueError("item %d: correspondences must be (n, 6)" % k)
+        arrs.append(a.reshape(-1, 6))
+    offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
+    if arrs:
+        offsets[1:] = np.cumsum([a.shape[0] for a in arrs])
+    corresp = np.concatenate(arrs, axis=0) if arrs else np.zeros((0, 6))
+    return np.ascontiguousarray(corresp), offsets
+
+
+def check_offsets(offsets):
+    """Validate a host offsets array (B + 1 int64, offsets[0] >= 0, non-decreasing); returns n_max (0 for an empty batch)."""
+    offsets = np.asarray(offsets)
+    if offsets.ndim != 1 or offsets.shape[0] < 1:
+        raise ValueError("offsets must be a 1-D array of B + 1 entries")
+    if not np.issubdtype(offsets.dtype, np.integer):
+        raise ValueError("offsets must be integers")
+    if offsets[0] < 0:
+        raise ValueError("offsets[0] must be >= 0")
+    n = np.diff(offsets.astype(np.int64))
+    if n.size and n.min() < 0:
+        raise ValueError("offsets must not decrease (item %d)" % int(np.argmin(n)))
+    return int(n.max()) if n.size else 0
 
 
 def _check(lib, rc, what):
@@ -332,6 +371,63 @@ class Context:
                    _raw=(Rt2, Rt3, T, rec))
         return out
 
+
+    def pose_batch_ragged(self, method, corresp, offsets, calm, reconst=True, n_max=None):
+        """One call for triplets with different correspondence counts (LinearTFT, LinearF): corresp (Ntot, 6) packed, offsets (B + 1,)
+        int64 with triplet b = corresp[offsets[b]:offsets[b + 1]] (see pack_ragged); calm (9, 3) shared or (B, 9, 3).  Each triplet's
+        outputs are bit-identical to pose_batch() on that triplet alone.  numpy in -> numpy out (host path; malformed offsets raise).
+        torch CUDA tensors in (offsets on the same device) -> torch tensors out, asynchronous on the current stream; n_max bounds every
+        n_b (a larger one marks the item ST_BAD_OFFSETS) -- pass it to avoid the one synchronisation that computes it from the offsets.
+        Returns dict(R_t_2 (B,3,4), R_t_3 (B,3,4), T (B,3,3,3), Reconst (Ntot,3) packed or None, iter (B,), status (B,))."""
+        if method not in METHOD_IDS:
+            raise ValueError("unknown method %r" % (method,))
+        mid = METHOD_IDS[method]
+        if isinstance(corresp, np.ndarray):
+            corresp = np.ascontiguousarray(corresp, dtype=np.float64).reshape(-1, 6)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            check_offsets(offsets)
+            B = offsets.shape[0] - 1
+            if offsets[-1] > corresp.shape[0]:
+                raise ValueError("offsets[-1] = %d beyond the %d packed correspondences" % (offsets[-1], corresp.shape[0]))
+            calm_cm, stride = self._calm_cm_np(calm, B)
+            Rt2 = np.empty((B, 12)); Rt3 = np.empty((B, 12)); T = np.empty((B, 27))
+            rec = np.full((corresp.shape[0], 3), np.nan) if reconst else None
+            it = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32)
+            ptr = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None else None
+            _check(self.lib, self.lib.tff_pose_batch_ragged_host(self.handle, mid, ptr(corresp), ptr(offsets), ptr(calm_cm), stride, B, ptr(Rt2),
+                                                                 ptr(Rt3), ptr(T), ptr(rec), ptr(it), ptr(st)), "tff_pose_batch_ragged_host")
+            return dict(R_t_2=Rt2.reshape(B, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(B, 4, 3).transpose(0, 2, 1),
+                        T=T.reshape(B, 3, 3, 3).transpose(0, 3, 2, 1), Reconst=rec, iter=it, status=st)
+        if not (corresp.is_cuda and corresp.dtype == torch.float64 and corresp.is_contiguous()):
+            raise ValueError("corresp must be a contiguous float64 CUDA tensor of shape (Ntot, 6)")
+        dev = corresp.device
+        if not (offsets.is_cuda and offsets.device == dev and offsets.dtype == torch.int64 and offsets.dim() == 1):
+            raise ValueError("offsets must be a 1-D int64 tensor on the device of corresp")
+        offsets = offsets.contiguous()
+        B = offsets.shape[0] - 1
+        if n_max is None:                                                   # one synchronisation; pass n_max to avoid it
+            n_max = max(0, int((offsets[1:] - offsets[:-1]).max().item())) if B > 0 else 0   # (negative n_b: ST_BAD_OFFSETS per item)
+        if isinstance(calm, np.ndarray):
+            calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
+        if not isinstance(calm, torch.Tensor) or tuple(calm.shape) not in ((9, 3), (B, 9, 3)):
+            raise ValueError("CalM must be a (9, 3) or (B, 9, 3) array or tensor")
+        if tuple(calm.shape) == (9, 3):
+            calm_cm, stride = calm.t().contiguous().reshape(27), 0
+        else:
+            calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(B * 27), 27
+        calm_cm = calm_cm.to(device=dev, dtype=torch.float64)
+        Rt2 = torch.empty((B, 12), dtype=torch.float64, device=dev)
+        Rt3 = torch.empty((B, 12), dtype=torch.float64, device=dev)
+        T = torch.empty((B, 27), dtype=torch.float64, device=dev)
+        rec = torch.full((corresp.shape[0], 3), float("nan"), dtype=torch.float64, device=dev) if reconst else None
+        it = torch.zeros(B, dtype=torch.int32, device=dev)
+        st = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        _check(self.lib, self.lib.tff_pose_batch_ragged_dev(self.handle, mid, p(corresp), p(offsets), int(n_max), p(calm_cm), stride, B, p(Rt2),
+                                                            p(Rt3), p(T), p(rec), p(it), p(st)), "tff_pose_batch_ragged_dev")
+        return dict(R_t_2=Rt2.reshape(B, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(B, 4, 3).transpose(1, 2),
+                    T=T.reshape(B, 3, 3, 3).permute(0, 3, 2, 1), Reconst=rec, iter=it, status=st, _raw=(Rt2, Rt3, T, rec))
 
     # ---- building blocks (torch CUDA tensors or numpy arrays in; torch CUDA tensors out) ------------
     def _t(self, a, dtype=None):

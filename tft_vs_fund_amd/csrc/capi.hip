@@ -6,9 +6,11 @@
 #include <type_traits>
 #include <vector>
 #include <cstdio>
+#include <climits>
 #include <cstring>
 #include "../../include/tftfund.h"
 #include "launch.h"
+#include "ragged_kernel.h"
 
 namespace {
 
@@ -56,6 +58,7 @@ struct tff_ctx {
     int exact_below = tff::EXACT_BELOW_N;   // TFF_OPT_EXACT_BELOW
     int stage = -1;
     DevBuf in, calm, out, idx, scratch_status, gh_rec, gh_topt, gh_init, spill, pre_rec, retry;
+    DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
     const int32_t* sample_idx = nullptr;   // set around a *_sampled_dev call
     int32_t sample_ns = 0;                 //   size of the scene the indices refer to
     double* init_p = nullptr; double* init_x = nullptr;   // set around tff_pi_pose_batch_debug_dev
@@ -544,6 +547,132 @@ int pose_batch_host(pose_launcher launch, tff_ctx* c, const double* corresp, con
     return 0;
 }
 
+
+// ---- ragged batches (tff_pose_batch_ragged_*; plan in ragged_kernel.h) ------------------------------------------------------------------------
+// Triplet b of a ragged batch takes the kernel chain the fixed-N launcher takes for its own n_b: the row kernel of its tier (exact tiers for
+// n < exact_below or TFF_OPT_SOLVER = 1, fast tiers otherwise), then the one-triplet exact kernel over the retry list.  The plan buckets the items
+// by n, so each wavefront of a row kernel carries one n and runs exactly the fixed-N instructions for it; the fix-up kernel reads n and the
+// LDS staging decision per triplet.  No host synchronisation: the plan's counts stay on the device.
+constexpr int32_t RAGGED_MAX_N = 1 << 24;   // bounds the plan's buckets (n_max + 1 of them)
+
+struct RaggedRoute {                       // the kernels of one method's ragged chain
+    void (*fast)(const tff::LinearTftArgs);
+    void (*exact)(const tff::LinearTftArgs);
+    void (*fixup)(const tff::LinearTftArgs);
+    lds_fn fix_lds;
+    int stage_max_n;
+};
+bool ragged_route(int32_t method, RaggedRoute* r) {
+    switch (method) {
+        case TFF_METHOD_LINEAR_TFT:
+            *r = RaggedRoute{tff::k_linear_tft_pose_rows<false, true>, tff::k_linear_tft_pose_rows_exact_ragged, tff::k_linear_tft_pose<true, true>,
+                             tff::pose_lds_bytes, tff::STAGE_MAX_N_TFT};
+            return true;
+        case TFF_METHOD_LINEAR_F:
+            *r = RaggedRoute{tff::k_linear_f_pose_rows_ragged, tff::k_linear_f_pose_rows_exact_ragged, tff::k_f_pose<true, 0, true>,
+                             tff::f_pose_lds_bytes, tff::STAGE_MAX_N_F};
+            return true;
+        default:
+            return false;
+    }
+}
+
+int check_ragged(const tff_ctx* c, int32_t method, const void* corresp, const void* offsets, int32_t n_max, const void* calm, int64_t calm_stride,
+                 int64_t B, RaggedRoute* route) {
+    if (!c) return fail(TFF_E_INVALID, "null context");
+    if (method < TFF_METHOD_LINEAR_TFT || method > TFF_METHOD_OPTIM_F) return fail(TFF_E_INVALID, "unknown method");
+    if (B < 0 || n_max < 0) return fail(TFF_E_INVALID, "negative batch size or n_max");
+    if (n_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "ragged batches: n_max above 2^24");
+    if (B >= (1L << tff::RETRY_HINT_SHIFT)) return fail(TFF_E_INVALID, "ragged batches: at most 2^28 - 1 triplets per call");
+    if (!offsets) return fail(TFF_E_INVALID, "null offsets");
+    if (B > 0 && (!corresp || !calm)) return fail(TFF_E_INVALID, "null input pointer");
+    if (calm_stride != 0 && calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
+    if (c->rows == 0) return fail(TFF_E_INVALID, "ragged batches run on the row kernels: TFF_OPT_ROWS = 0 is not supported");
+    if (c->kernel_variant == 1) return fail(TFF_E_INVALID, "ragged batches: TFF_OPT_KERNEL = 1 (fused single-wavefront kernels) is not supported");
+    if (!ragged_route(method, route))
+        return fail(TFF_E_INVALID, "ragged batches are implemented for LinearTFT and LinearF only; group this method's triplets by N");
+    return 0;
+}
+
+// largest n <= n_max whose fixed-N call stages the correspondences of the fix-up kernel in LDS (launch_pose_rows), -1 if none: the rule holds
+// for every n up to some bound, so a bisection finds it
+int ragged_stage_upto(const tff_ctx* c, const RaggedRoute& r, int flags, int32_t n_max) {
+    auto staged = [&](int n) {
+        const int f = staged_flags(c, n, flags, true, r.stage_max_n);
+        return (f & tff::FLAG_STAGE_LDS) && r.fix_lds(n, f, true) <= LDS_LIMIT;
+    };
+    if (!staged(0)) return -1;
+    int lo = 0, hi = n_max;                // staged(lo) holds
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (staged(mid)) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+int launch_ragged(tff_ctx* c, int32_t method, const double* corresp, const int64_t* offsets, int32_t n_max, const double* calm, int64_t calm_stride,
+                  int64_t B, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter, int32_t* status) {
+    RaggedRoute r;
+    if (int e = check_ragged(c, method, corresp, offsets, n_max, calm, calm_stride, B, &r)) return e;
+    TFF_LOCK(c);
+    if (B == 0) return 0;
+    if (!Rt2 || !Rt3 || !T) return fail(TFF_E_INVALID, "null output pointer");
+    TFF_HIP(hipSetDevice(c->device));
+    if (!status) {
+        if (int e = c->scratch_status.reserve((size_t)B * sizeof(int32_t))) return e;
+        status = (int32_t*)c->scratch_status.p;
+    }
+    // the plan: hist | fill | start (n_max + 1 each) | route (4) | slot list
+    const size_t nb = (size_t)n_max + 1;
+    const long slots = tff::ragged_slots((long)B, n_max);
+    if (int e = c->ragged.reserve((3 * nb + 4 + (size_t)slots) * sizeof(int32_t))) return e;
+    int* ws = (int*)c->ragged.p;
+    tff::RaggedPlanArgs pa{(const long*)offsets, (long)B, n_max, 0, ws, ws + nb, ws + 2 * nb, ws + 3 * nb, ws + 3 * nb + 4, Rt2, Rt3, T, iter, status};
+    pa.split = (c->solver != 0 || c->exact_below > n_max) ? n_max + 1 : (c->exact_below > 0 ? c->exact_below : 0);
+    TFF_HIP(hipMemsetAsync(ws, 0, 2 * nb * sizeof(int32_t), c->stream));
+    const unsigned items = (unsigned)((B + 255) / 256);
+    hipLaunchKernelGGL(tff::k_ragged_count, dim3(items), dim3(256), 0, c->stream, pa);
+    TFF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(tff::k_ragged_scan, dim3(1), dim3(tff::RAGGED_SCAN_THREADS), 0, c->stream, pa);
+    TFF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(tff::k_ragged_scatter, dim3(items), dim3(256), 0, c->stream, pa);
+    TFF_HIP(hipGetLastError());
+    // the retry list of the fix-up, as launch_pose_rows keeps it
+    {
+        void* before = c->retry.p;
+        if (int e = c->retry.reserve(((size_t)B + 2) * sizeof(int32_t))) return e;
+        if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
+    }
+    tff::LinearTftArgs a{corresp, calm, (long)calm_stride, (long)B, 0, base_flags(c, reconst != nullptr), Rt2, Rt3, T, reconst, iter, status};
+    a.retry_count = (int*)c->retry.p + c->retry_parity;
+    a.retry_zero = (int*)c->retry.p + (1 - c->retry_parity);
+    a.retry_list = (int*)c->retry.p + 2;
+    a.offsets = (const long*)offsets;
+    a.rlist = pa.list;
+    a.stage_upto = -1;
+    const unsigned grid = tff::rows_grid(slots);
+    if (pa.split > 0) {                    // some n may be below the split: the exact tiers' row kernel over [0, mid)
+        a.rrange = pa.route;
+        hipLaunchKernelGGL(r.exact, dim3(grid), dim3(64), tff::rows_lds_bytes(), c->stream, a);
+        TFF_HIP(hipGetLastError());
+    }
+    if (pa.split <= n_max) {               // ... and the fast tiers' over [mid, total)
+        a.rrange = pa.route + 2;
+        hipLaunchKernelGGL(r.fast, dim3(grid), dim3(64), tff::rows_lds_bytes(), c->stream, a);
+        TFF_HIP(hipGetLastError());
+    }
+    c->retry_parity ^= 1;
+    a.rrange = nullptr;
+    a.flags |= tff::FLAG_ONLY_RETRY;
+    a.stage_upto = ragged_stage_upto(c, r, a.flags, n_max);
+    const size_t lds = a.stage_upto >= 0 ? r.fix_lds(a.stage_upto, a.flags | tff::FLAG_STAGE_LDS, true) : r.fix_lds(0, a.flags, true);
+    if (int e = ensure_lds(r.fixup, lds)) return e;
+    const long fix = 2 * FIXUP_GRID;
+    hipLaunchKernelGGL(r.fixup, dim3((unsigned)(B < fix ? B : fix)), dim3(64), lds, c->stream, a);
+    TFF_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // BundleAdjustment as the reference writes it, M = 2 .. 6 views, MATLAB's own array layouts (csrc/ba_views_kernel.h)
@@ -567,7 +696,7 @@ static int check_views(const tff_ctx* c, int32_t M, const void* calm, int64_t ca
 
 extern "C" {
 
-int tff_version(void) { return 100; }
+int tff_version(void) { return 101; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -592,7 +721,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
-    c->in.release(); c->calm.release(); c->out.release(); c->idx.release(); c->scratch_status.release(); c->gh_rec.release(); c->gh_topt.release(); c->gh_init.release(); c->spill.release(); c->pre_rec.release(); c->retry.release();
+    c->in.release(); c->calm.release(); c->out.release(); c->idx.release(); c->scratch_status.release(); c->gh_rec.release(); c->gh_topt.release(); c->gh_init.release(); c->spill.release(); c->pre_rec.release(); c->retry.release(); c->ragged.release(); c->ragged_off.release();
     delete c;
 }
 
@@ -663,6 +792,63 @@ int tff_linear_tft_pose_batch_dev(tff_ctx* c, const double* corresp, const doubl
                                   int32_t N, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter,
                                   int32_t* status) {
     return launch_linear_tft(c, corresp, calm, calm_stride, B, N, Rt2, Rt3, T, reconst, iter, status, nullptr);
+}
+
+int tff_pose_batch_ragged_dev(tff_ctx* c, int32_t method, const double* corresp, const int64_t* offsets, int32_t n_max, const double* calm,
+                              int64_t calm_stride, int64_t B, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter, int32_t* status) {
+    return launch_ragged(c, method, corresp, offsets, n_max, calm, calm_stride, B, Rt2, Rt3, T, reconst, iter, status);
+}
+
+// host pointers: the offsets are checked here (TFF_E_INVALID before any work), the packed range offsets[0] .. offsets[B] goes over as one copy
+int tff_pose_batch_ragged_host(tff_ctx* c, int32_t method, const double* corresp, const int64_t* offsets, const double* calm, int64_t calm_stride,
+                               int64_t B, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter, int32_t* status) {
+    if (!offsets) return fail(TFF_E_INVALID, "null offsets");
+    if (B < 0) return fail(TFF_E_INVALID, "negative batch size");
+    int64_t n_max = 0;
+    if (offsets[0] < 0) return fail(TFF_E_INVALID, "offsets[0] < 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
+        if (n < 0) return fail(TFF_E_INVALID, "offsets must not decrease");
+        if (n > n_max) n_max = n;
+    }
+    if (n_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "ragged batches: a triplet with more than 2^24 correspondences");
+    RaggedRoute route;
+    if (int r = check_ragged(c, method, corresp, offsets, (int32_t)n_max, calm, calm_stride, B, &route)) return r;
+    TFF_LOCK(c);
+    if (B == 0) return 0;
+    if (!Rt2 || !Rt3 || !T) return fail(TFF_E_INVALID, "null output pointer");
+    TFF_HIP(hipSetDevice(c->device));
+    const size_t first = (size_t)offsets[0], total = (size_t)offsets[B];
+    const size_t nin = total * 6 * sizeof(double);
+    const size_t ncal = (calm_stride ? (size_t)B : 1) * 27 * sizeof(double);
+    const size_t per_out = (12 + 12 + 27) * sizeof(double);
+    if (int r = c->in.reserve(nin ? nin : 8)) return r;
+    if (int r = c->calm.reserve(ncal)) return r;
+    if (int r = c->out.reserve((size_t)B * per_out + (reconst ? total * 3 * sizeof(double) : 0))) return r;
+    if (int r = c->idx.reserve((size_t)B * 2 * sizeof(int32_t))) return r;
+    if (int r = c->ragged_off.reserve(((size_t)B + 1) * sizeof(int64_t))) return r;
+    double* d_in = (double*)c->in.p;
+    double* d_cal = (double*)c->calm.p;
+    double* d_Rt2 = (double*)c->out.p;
+    double* d_Rt3 = d_Rt2 + (size_t)B * 12;
+    double* d_T = d_Rt3 + (size_t)B * 12;
+    double* d_rec = reconst ? d_T + (size_t)B * 27 : nullptr;
+    int32_t* d_it = (int32_t*)c->idx.p;
+    int32_t* d_st = d_it + B;
+    int64_t* d_off = (int64_t*)c->ragged_off.p;
+    if (total > first) TFF_HIP(hipMemcpyAsync(d_in + 6 * first, corresp + 6 * first, (total - first) * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(d_cal, calm, ncal, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(d_off, offsets, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (int r = launch_ragged(c, method, d_in, d_off, (int32_t)n_max, d_cal, calm_stride, B, d_Rt2, d_Rt3, d_T, d_rec, d_it, d_st)) return r;
+    TFF_HIP(hipMemcpyAsync(Rt2, d_Rt2, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(Rt3, d_Rt3, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(T, d_T, (size_t)B * 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (reconst && total > first)
+        TFF_HIP(hipMemcpyAsync(reconst + 3 * first, d_rec + 3 * first, (total - first) * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (iter) TFF_HIP(hipMemcpyAsync(iter, d_it, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (status) TFF_HIP(hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int tff_linear_tft_pose_batch_debug_dev(tff_ctx* c, const double* corresp, const double* calm, int64_t calm_stride,

@@ -436,7 +436,8 @@ __device__ inline int optim_f_refine(PoseLds* w, OptimFLds* og, double* oxi, con
 }
 
 // METHOD 0: LinearFPoseEstimation; METHOD 1: OptimFPoseEstimation (F_methods/OptimFPoseEstimation.m:44-73)
-template <bool JAC, int METHOD>
+// RAGGED (METHOD 0): the fix-up of a ragged batch, as k_linear_tft_pose<true, true>
+template <bool JAC, int METHOD, bool RAGGED = false>
 __global__ void __launch_bounds__(64, (METHOD == 1 && !JAC) ? 3 : 2) k_f_pose(const LinearTftArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     PoseLds* w = reinterpret_cast<PoseLds*>(smem);
@@ -451,16 +452,17 @@ __global__ void __launch_bounds__(64, (METHOD == 1 && !JAC) ? 3 : 2) k_f_pose(co
     for (long wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
         const long b = (a.retry_list && (a.flags & FLAG_ONLY_RETRY)) ? (long)(a.retry_list[wi] & RETRY_INDEX_MASK) : wi;
         if ((a.flags & FLAG_ONLY_RETRY) && a.status[b] != ST_RETRY) continue;      // wave-uniform
-        const int N = opaque_int(a.N);                                       // (not hoisted out of the one-trip triplet loop: tft_kernel.h)
+        const int N = RAGGED ? ragged_n(a.offsets, b) : opaque_int(a.N);     // (not hoisted out of the one-trip triplet loop: tft_kernel.h)
         double* dbg = a.dbg ? a.dbg + b * DBG_STRIDE : nullptr;
-        const double* src = a.corresp + b * 6 * (long)N;
+        const long rb = RAGGED ? a.offsets[b] : 0;                           // (ragged: the triplet's first correspondence)
+        const double* src = a.corresp + (RAGGED ? 6 * rb : b * 6 * (long)N);
         const double* pts = src;
         wave_sync();
         bool bad_index = false;
         if (a.sample_idx) {
             bad_index = gather_points(a.corresp, a.sample_idx + b * (long)N, lds_pts, N, a.sample_ns);
             pts = lds_pts;
-        } else if (a.flags & FLAG_STAGE_LDS) {
+        } else if (RAGGED ? (ragged_flags(a, N) & FLAG_STAGE_LDS) : (a.flags & FLAG_STAGE_LDS)) {
             stage_points(src, lds_pts, N);
             pts = lds_pts;
         }
@@ -471,7 +473,7 @@ __global__ void __launch_bounds__(64, (METHOD == 1 && !JAC) ? 3 : 2) k_f_pose(co
             const double qnan = __longlong_as_double(0x7ff8000000000000LL);
             if (lane < 12) { a.Rt2[b * 12 + lane] = qnan; a.Rt3[b * 12 + lane] = qnan; }
             if (lane < 27) a.T[b * 27 + lane] = qnan;
-            if (a.reconst) for (int i = lane; i < 3 * N; i += WAVE) a.reconst[b * 3 * (long)N + i] = qnan;
+            if (a.reconst) for (int i = lane; i < 3 * N; i += WAVE) a.reconst[(RAGGED ? 3 * rb : b * 3 * (long)N) + i] = qnan;
         } else {
             normalise3(pts, N, w->nrm);                                      // LinearFPoseEstimation.m:46-48 / optimF.m:46-47
             normalise3(pts, N, w->nrm2, w->nrm);                             // linearF.m:45-46 (on the normalised points)
@@ -519,7 +521,7 @@ __global__ void __launch_bounds__(64, (METHOD == 1 && !JAC) ? 3 : 2) k_f_pose(co
                 if (fine) {
                     if (lane == 0) compose_camera_from_pose(load_K(w->calm, 2), w->Rt[1], w->Pfin[2]);   // K3 [R3 | lam t3]
                     wave_sync();
-                    if (a.reconst) fine = tri_pass<JAC>(w, pts, N, TRI_RECONST, 1, w->Pfin[1], w->Pfin[2], a.reconst + b * 3 * (long)N);
+                    if (a.reconst) fine = tri_pass<JAC>(w, pts, N, TRI_RECONST, 1, w->Pfin[1], w->Pfin[2], a.reconst + (RAGGED ? 3 * rb : b * 3 * (long)N));
                 }
                 if (!fine) {
                     status = ST_RETRY;                                       // a fast tier gave up: redone by k_f_pose<true, .>
@@ -530,7 +532,7 @@ __global__ void __launch_bounds__(64, (METHOD == 1 && !JAC) ? 3 : 2) k_f_pose(co
                     if (lane < 27) a.T[b * 27 + lane] = w->T1[lane];
                     double chk = (lane < 12) ? w->Rt[0][lane] : ((lane < 24) ? w->Rt[1][lane - 12] : ((lane < 51) ? w->T1[lane - 24] : 0.0));
                     const bool bad = !(fabs(chk) <= 1.79e308);
-                    if (wave_any(bad)) { if (status == ST_OK) status = ST_NONFINITE; wave_nan_outputs(a.Rt2, a.Rt3, a.T, a.reconst, b, N); }
+                    if (wave_any(bad)) { if (status == ST_OK) status = ST_NONFINITE; ragged_nan_outputs<RAGGED>(a, b, rb, N); }
                 }
             }
         }

@@ -152,19 +152,20 @@ __device__ __forceinline__ bool rows_linear_f_middle(RowLds* w, RowRt* rt, doubl
     return ok && !bad;
 }
 
-__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows(const LinearTftArgs a) {
+template <bool RAGGED>
+__device__ __forceinline__ void linear_f_pose_rows(const LinearTftArgs& a) {
     TFF_DYNAMIC_LDS(double, smem);
     if (a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call; this call's was zeroed during the previous one)
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
     RowRt* rt = reinterpret_cast<RowRt*>(w->ov);
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
-        const int N = opaque_int(a.N);
-        const RowJob j = rows_begin(a, w, blk, N);
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(a, blk) < a.rrange[1] : blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
+        const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         int status;
         if (N < 8) {                                                         // linearF.m:35-37 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
-            rows_store_nan(a, j, N);
+            rows_store_nan<RAGGED>(a, j, N);
         } else {
             {
                 double cen[6];
@@ -174,7 +175,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows(const LinearTftArg
             wave_sync();
             bool ok = rows_linear_f_middle(w, rt, w->t, w->pa, j.dbg);       // (w->t: F21, F31)
             rows_recover_prepare(w, rt);
-            status = rows_pose_tail<true>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<true, false, RAGGED>(a, w, rt, j, N, ok);
         }
         if (p == 0 && j.valid) {
             if (a.iter) a.iter[j.b] = 0;                                     // LinearFPoseEstimation.m:77
@@ -183,6 +184,9 @@ __global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows(const LinearTftArg
         }
     }
 }
+__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows(const LinearTftArgs a) { linear_f_pose_rows<false>(a); }
+// a ragged batch (LinearTftArgs::offsets): the wave's four triplets are one slot of the bucket list, n is the slot's
+__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_ragged(const LinearTftArgs a) { linear_f_pose_rows<true>(a); }
 
 // M rows (correspondences base .. base + M - 1) of the N x 9 system of one view pair appended to the row's packed R: entry h1 (x) h2 at position 3a + b
 // (linearF.m:48-53), on the points normalised twice (LinearFPoseEstimation.m:46-48, linearF.m:45-46).
@@ -291,19 +295,20 @@ __device__ __forceinline__ bool rows_linear_f_middle_exact(RowLds* w, RowRt* rt,
     return ok;
 }
 
-__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_exact(const LinearTftArgs a) {
+template <bool RAGGED>
+__device__ __forceinline__ void linear_f_pose_rows_exact(const LinearTftArgs& a) {
     TFF_DYNAMIC_LDS(double, smem);
     if (a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call; this call's was zeroed during the previous one)
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
     RowRt* rt = reinterpret_cast<RowRt*>(w->ov);
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
-        const int N = opaque_int(a.N);
-        const RowJob j = rows_begin(a, w, blk, N);
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(a, blk) < a.rrange[1] : blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
+        const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         int status;
         if (N < 8) {                                                         // linearF.m:35-37
             status = ST_TOO_FEW;
-            rows_store_nan(a, j, N);
+            rows_store_nan<RAGGED>(a, j, N);
         } else {
             rows_stamp(j.dbg, 0);
             {
@@ -318,7 +323,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_exact(const Linear
             rows_stamp(j.dbg, 2);
             rows_recover_prepare(w, rt);
             rows_stamp(j.dbg, 10);
-            status = rows_pose_tail<true, true>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<true, true, RAGGED>(a, w, rt, j, N, ok);
         }
         if (p == 0 && j.valid) {
             if (a.iter) a.iter[j.b] = 0;                                     // LinearFPoseEstimation.m:77
@@ -327,5 +332,8 @@ __global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_exact(const Linear
         }
     }
 }
+__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_exact(const LinearTftArgs a) { linear_f_pose_rows_exact<false>(a); }
+// a ragged batch (LinearTftArgs::offsets): the wave's four triplets are one slot of the bucket list, n is the slot's
+__global__ void __launch_bounds__(64, 2) k_linear_f_pose_rows_exact_ragged(const LinearTftArgs a) { linear_f_pose_rows_exact<true>(a); }
 
 }  // namespace tff

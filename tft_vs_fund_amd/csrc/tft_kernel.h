@@ -71,6 +71,13 @@ struct LinearTftArgs {
     int* retry_list;
     int* retry_count;
     int* retry_zero;
+    // Ragged batches (the <..., RAGGED = true> kernels, ragged_kernel.h): triplet b owns the correspondences offsets[b] .. offsets[b+1] - 1 of the
+    // packed `corresp` (and the same range of 3-vectors of `reconst`); N is ignored.  The row kernels walk rlist[rrange[0] .. rrange[1]), slots
+    // of four with one n each (-1: a padding slot); the one-triplet fix-up kernels stage a triplet's correspondences in LDS iff n <= stage_upto.
+    const long* offsets;
+    const int* rlist;
+    const int* rrange;
+    int stage_upto;
 };
 
 // Inverse-iteration cap before a triplet is handed to the Jacobi fix-up pass: 300 iterations (~0.13 M
@@ -81,6 +88,18 @@ constexpr int EIG_MAXIT = 300;
 // bit 1: the 15-column one did); batches of 2^28 triplets and more go without the list (capi.hip)
 constexpr int RETRY_HINT_SHIFT = 28;
 constexpr int RETRY_INDEX_MASK = (1 << RETRY_HINT_SHIFT) - 1;
+
+// ragged batches: triplet b's correspondence count (wave-uniform), the flags of the fixed-N call for that count (staged in LDS iff
+// n <= stage_upto, as capi.hip decides for a fixed N), and the all-NaN outputs of a non-finite triplet (pose_common.h::wave_nan_outputs)
+__device__ __forceinline__ int ragged_n(const long* offsets, const long b) { return opaque_int(wave_uniform_i((int)(offsets[b + 1] - offsets[b]))); }
+__device__ __forceinline__ int ragged_flags(const LinearTftArgs& a, const int n) {
+    return opaque_int(n <= a.stage_upto ? (a.flags | FLAG_STAGE_LDS) : (a.flags & ~FLAG_STAGE_LDS));
+}
+template <bool RAGGED>
+__device__ __forceinline__ void ragged_nan_outputs(const LinearTftArgs& a, const long b, const long rb, const int N) {
+    if constexpr (RAGGED) wave_nan_outputs(a.Rt2 + b * 12, a.Rt3 + b * 12, a.T + b * 27, a.reconst ? a.reconst + 3 * rb : nullptr, 0, N);
+    else wave_nan_outputs(a.Rt2, a.Rt3, a.T, a.reconst, b, N);
+}
 
 // c-vector of a pair of 3-vectors (see header): bilinear weights of the q-monomials
 __device__ __forceinline__ void cvec(const double* a, const double* b, double (&c)[4]) {
@@ -455,7 +474,8 @@ __device__ inline int rt_from_tft_wave(PoseLds* w, const double* pts, int N, dou
     return st;
 }
 
-template <bool JAC>
+// RAGGED: the fix-up of a ragged batch (LinearTftArgs::offsets): the triplet's n and first correspondence from the offsets, its staging from stage_upto
+template <bool JAC, bool RAGGED = false>
 __global__ void __launch_bounds__(64, 2) k_linear_tft_pose(const LinearTftArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     PoseLds* w = reinterpret_cast<PoseLds*>(smem);
@@ -471,10 +491,11 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose(const LinearTftArgs a
         const int hint = JAC ? (int)((unsigned)entry >> RETRY_HINT_SHIFT) : 0;
         // (opaque: the loop makes one trip per workgroup; what the optimiser derives from N and the flags ahead of it -- N * 6, N < 7,
         // flag tests as scalar masks, ... -- would be computed in the pre-header and spilled across the whole body, see wave.h::lane_id)
-        const int N = opaque_int(a.N), flags = opaque_int(a.flags);
+        const int N = RAGGED ? ragged_n(a.offsets, b) : opaque_int(a.N), flags = RAGGED ? ragged_flags(a, N) : opaque_int(a.flags);
         if ((flags & FLAG_ONLY_RETRY) && a.status[b] != ST_RETRY) continue;        // wave-uniform
         double* dbg = a.dbg ? a.dbg + b * DBG_STRIDE : nullptr;
-        const double* src = a.corresp + b * 6 * (long)N;
+        const long rb = RAGGED ? a.offsets[b] : 0;                           // (ragged: the triplet's first correspondence)
+        const double* src = a.corresp + (RAGGED ? 6 * rb : b * 6 * (long)N);
         const double* pts = src;
         wave_sync();
         bool bad_index = false;
@@ -493,7 +514,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose(const LinearTftArgs a
             const double qnan = __longlong_as_double(0x7ff8000000000000LL);
             if (lane < 12) { a.Rt2[b * 12 + lane] = qnan; a.Rt3[b * 12 + lane] = qnan; }
             if (lane < 27) a.T[b * 27 + lane] = qnan;
-            if (a.reconst) for (int i = lane; i < 3 * N; i += WAVE) a.reconst[b * 3 * (long)N + i] = qnan;
+            if (a.reconst) for (int i = lane; i < 3 * N; i += WAVE) a.reconst[(RAGGED ? 3 * rb : b * 3 * (long)N) + i] = qnan;
         } else {
             normalise3(pts, N, w->nrm);                                      // LinearTFTPoseEstimation.m:45-47
             if (dbg && lane < 9) dbg[71 + lane] = w->nrm[lane];
@@ -504,7 +525,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose(const LinearTftArgs a
                 transform_tft_inverse(w->t, w->T1, w->Lp, [w](int v) { return normal_matrix(w->nrm, v); });   // :53
                 status = rt_from_tft_wave<JAC>(w, pts, N, dbg, &ok);         // :56
             }
-            if (ok && a.reconst) ok = final_reconst<JAC>(w, pts, N, a.reconst + b * 3 * (long)N);   // :59-60
+            if (ok && a.reconst) ok = final_reconst<JAC>(w, pts, N, a.reconst + (RAGGED ? 3 * rb : b * 3 * (long)N));   // :59-60
             if (!ok) {
                 status = ST_RETRY;                                           // redone by k_linear_tft_pose<true>
             } else {
@@ -514,7 +535,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose(const LinearTftArgs a
                 // non-finite outputs -> status 2
                 double chk = (lane < 12) ? w->Rt[0][lane] : ((lane < 24) ? w->Rt[1][lane - 12] : ((lane < 51) ? w->T1[lane - 24] : 0.0));
                 const bool bad = !(fabs(chk) <= 1.79e308);
-                if (wave_any(bad)) { if (status == ST_OK) status = ST_NONFINITE; wave_nan_outputs(a.Rt2, a.Rt3, a.T, a.reconst, b, N); }
+                if (wave_any(bad)) { if (status == ST_OK) status = ST_NONFINITE; ragged_nan_outputs<RAGGED>(a, b, rb, N); }
             }
         }
         if (lane == 0) {

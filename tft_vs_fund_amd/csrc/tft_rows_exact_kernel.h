@@ -169,20 +169,21 @@ __device__ __forceinline__ bool rows_linear_tft_middle_exact(RowLds* w, const Ro
     return ok;
 }
 
-__global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows_exact(const LinearTftArgs a) {
+template <bool RAGGED>
+__device__ __forceinline__ void linear_tft_pose_rows_exact(const LinearTftArgs& a) {
     TFF_DYNAMIC_LDS(double, smem);
     if (a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call; this call's was zeroed during the previous one)
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
     RowRt* rt = reinterpret_cast<RowRt*>(w->ov);
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
-        const int N = opaque_int(a.N);
-        const RowJob j = rows_begin(a, w, blk, N);
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(a, blk) < a.rrange[1] : blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
+        const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         double* dbg = j.dbg;
         int status, hint = 0;
         if (N < 7) {                                                         // experiments.m:99 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
-            rows_store_nan(a, j, N);
+            rows_store_nan<RAGGED>(a, j, N);
         } else {
             rows_stamp(dbg, 0);
             {
@@ -199,7 +200,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows_exact(const Line
             rows_transform_tft_inverse(w->t, rt->T1, rt->mats, [w](int v) { return normal_matrix(w->nrm, v); });   // :53
             ok = rows_rt_prepare<true>(w, rt, dbg) && ok;                    // :56
             rows_stamp(dbg, 10);
-            status = rows_pose_tail<false, true>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<false, true, RAGGED>(a, w, rt, j, N, ok);
         }
         if (p == 0 && j.valid) {
             if (a.iter) a.iter[j.b] = 0;                                     // :62
@@ -208,5 +209,8 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows_exact(const Line
         }
     }
 }
+__global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows_exact(const LinearTftArgs a) { linear_tft_pose_rows_exact<false>(a); }
+// a ragged batch (LinearTftArgs::offsets): the wave's four triplets are one slot of the bucket list, n is the slot's
+__global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows_exact_ragged(const LinearTftArgs a) { linear_tft_pose_rows_exact<true>(a); }
 
 }  // namespace tff

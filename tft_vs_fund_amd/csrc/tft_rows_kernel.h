@@ -781,6 +781,7 @@ struct RowJob {
     bool bad_index;        // sampled hypotheses: an index outside the scene
     double* dbg;
     RowSrc src;
+    long base = 0;         // ragged batches: the triplet's first correspondence in the packed arrays
 };
 // the row's triplet, its correspondences and calibration (-> w->calm)
 __device__ __forceinline__ RowJob rows_begin(const LinearTftArgs& a, RowLds* w, const long blk, const int N) {
@@ -805,6 +806,33 @@ __device__ __forceinline__ RowJob rows_begin(const LinearTftArgs& a, RowLds* w, 
     if (p < 11) w->calm[16 + p] = a.calm[j.b * a.calm_stride + 16 + p];
     return j;
 }
+// Ragged batches: the wave's four slots of rlist (one bucket of equal n, see ragged_kernel.h).  A padding slot (-1) repeats the slot's first triplet --
+// as a tail row repeats the batch's last one -- and stores nothing.
+__device__ __forceinline__ long rows_ragged_slot(const LinearTftArgs& a, const long blk) { return a.rrange[0] + blk * ROW_TRIPLETS; }
+__device__ __forceinline__ int rows_ragged_n(const LinearTftArgs& a, const long blk) {
+    const long b0 = a.rlist[rows_ragged_slot(a, blk)];
+    return opaque_int(wave_uniform_i((int)(a.offsets[b0 + 1] - a.offsets[b0])));
+}
+__device__ __forceinline__ RowJob rows_begin_ragged(const LinearTftArgs& a, RowLds* w, const long blk) {
+    const int lane = lane_id(), p = lane & 15, row = lane >> 4;
+    const long slot = rows_ragged_slot(a, blk);
+    const int e = a.rlist[slot + row];
+    RowJob j;
+    j.valid = e >= 0;
+    j.b = j.valid ? (long)e : (long)a.rlist[slot];
+    j.base = a.offsets[j.b];
+    j.dbg = nullptr;
+    j.src.idx = nullptr;
+    j.src.pts = a.corresp + 6 * j.base;
+    j.src.ns = 0;
+    j.src.sampled = false;
+    wave_sync();
+    j.bad_index = false;
+    w->calm[p] = a.calm[j.b * a.calm_stride + p];
+    if (p < 11) w->calm[16 + p] = a.calm[j.b * a.calm_stride + 16 + p];
+    return j;
+}
+template <bool RAGGED = false>
 __device__ __forceinline__ void rows_store_nan(const LinearTftArgs& a, const RowJob& j, const int N) {
     const int p = rows_p();
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
@@ -812,7 +840,7 @@ __device__ __forceinline__ void rows_store_nan(const LinearTftArgs& a, const Row
         if (p < 12) { a.Rt2[j.b * 12 + p] = qnan; a.Rt3[j.b * 12 + p] = qnan; }
         a.T[j.b * 27 + p] = qnan;
         if (p < 11) a.T[j.b * 27 + 16 + p] = qnan;
-        if (a.reconst) for (int i = p; i < 3 * N; i += ROWL) a.reconst[j.b * 3 * (long)N + i] = qnan;
+        if (a.reconst) for (int i = p; i < 3 * N; i += ROWL) a.reconst[(RAGGED ? 3 * j.base : j.b * 3 * (long)N) + i] = qnan;
     }
 }
 
@@ -867,7 +895,7 @@ __device__ __forceinline__ void rows_vote_exact_pair(const RowSrc& s, const int 
 
 // EXACT: every score is evaluated (all four candidates), an uncertified one is recomputed by rows_vote_exact, the t3 scale and Reconst take the
 // certified DLT ladder -- the row then fails only on what the caller's exact tiers reported.
-template <bool T_FROM_CAMERAS, bool EXACT = false>
+template <bool T_FROM_CAMERAS, bool EXACT = false, bool RAGGED = false>
 __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w, RowRt* rt, const RowJob& j, const int N, bool ok) {
     const int p = rows_p();
     double* dbg = j.dbg;
@@ -994,7 +1022,7 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
         double n0, d0;
         // only a row that owns a live triplet stores: a tail row, a failed triplet (its Reconst is NaN) and a row that is merely carried
         // along by a neighbour's exact-tier redo (k_gh_finish_rows) leave Reconst alone -- a triplet's bits never depend on its neighbours
-        double* rec = (j.valid && !j.bad_index && !nonfinite) ? a.reconst + b * 3 * (long)N : nullptr;
+        double* rec = (j.valid && !j.bad_index && !nonfinite) ? a.reconst + (RAGGED ? 3 * j.base : b * 3 * (long)N) : nullptr;
         const bool conv = rows_tri_pass<TRI_RECONST, EXACT>(j.src, N, rt->Pfin[0], rt->Pfin[1], rt->Pfin[2], rec, n0, d0);
         ok = ok && conv;
     }
@@ -1002,7 +1030,7 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
     else if (!ok) status = ST_RETRY;                                         // redone by the exact kernel
     else if (nonfinite && status == ST_OK) status = ST_NONFINITE;            // non-finite outputs -> status 2
     if (j.bad_index || (ok && nonfinite)) {
-        rows_store_nan(a, j, N);                                             // (stores only for a row that owns a triplet)
+        rows_store_nan<RAGGED>(a, j, N);                                     // (stores only for a row that owns a triplet)
     } else {
         const bool store = j.valid && ok;                                    // per row
 #pragma unroll
@@ -1018,22 +1046,23 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
 
 // PRE: the normalisations and moment sums come from k_tft_moments (a.pre) instead of the two data passes: the kernel starts at linearTFT's solve
 // and touches the correspondences in the vote pass only (and for Reconst).
-template <bool PRE>
+// RAGGED: a ragged batch (LinearTftArgs::offsets; PRE = false): the wave's four triplets are one slot of the bucket list, n is the slot's.
+template <bool PRE, bool RAGGED = false>
 __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows(const LinearTftArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     if (a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call; this call's was zeroed during the previous one)
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
     RowRt* rt = reinterpret_cast<RowRt*>(w->ov);
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
-        const int N = opaque_int(a.N);
-        const RowJob j = rows_begin(a, w, blk, N);
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(a, blk) < a.rrange[1] : blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
+        const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         double* dbg = j.dbg;
         rows_stamp(dbg, 0);
         int status;
         if (N < 7) {                                                         // experiments.m:99 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
-            rows_store_nan(a, j, N);
+            rows_store_nan<RAGGED>(a, j, N);
         } else {
             if constexpr (PRE) {
                 rows_load_pre(a.pre, j.b, w->mom, w->nrm);
@@ -1054,7 +1083,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows(const LinearTftA
             rows_transform_tft_inverse(w->t, rt->T1, rt->mats, [w](int v) { return normal_matrix(w->nrm, v); });   // :53
             ok = rows_rt_prepare(w, rt, dbg) && ok;                          // :56
             rows_stamp(dbg, 10);
-            status = rows_pose_tail<false>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<false, false, RAGGED>(a, w, rt, j, N, ok);
         }
         if (p == 0 && j.valid) {
             if (a.iter) a.iter[j.b] = 0;                                     // :62
