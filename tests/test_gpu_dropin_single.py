@@ -1,6 +1,6 @@
 """The MEX drop-in's call pattern (reference: experiments.m:108, `[R_t_2,R_t_3,Reconst,T,iter] = Method(Corresp,CalM)` on ONE
 triplet): every method called with B = 1 on a FRESH context with the library's default options -- no TFF_OPT_* set, so the route is whatever
-`capi.hip::rows_for` picks for a batch of one -- against the committed goldens: the linear methods and OptimF against the oracle fixtures
+`capi.hip::use_rows` picks for a batch of one -- against the committed goldens: the linear methods and OptimF against the oracle fixtures
 (1e-9 / 1e-8), the five Gauss-Helmert methods against the 50-digit fixtures at 1e-9 with the SAME iteration count
 (TFT_methods/ResslTFTPoseEstimation.m:47-105, Optimization/Gauss_Helmert.m:49-82)."""
 import os

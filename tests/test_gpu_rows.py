@@ -200,7 +200,7 @@ def test_default_route_is_the_row_kernels_at_any_batch_size(method):
                                     "OptimFPoseEstimation", "LinearTFTPoseEstimation", "LinearFPoseEstimation"])
 def test_iterative_methods_do_not_depend_on_the_batch_a_triplet_arrives_in(method):
     """(All eight methods since the end of round 5: the linear ones no longer pick their kernel by batch size either.)  The iterative methods amplify a last-bit difference of their start (the exit test of Gauss_Helmert.m:71-82 can flip on it), so the library's
-    DEFAULT route for them must not depend on the batch size (capi.hip::rows_for_iterative): the same 40 triplets alone, at the head of a batch
+    DEFAULT route for them must not depend on the batch size (capi.hip::use_rows): the same 40 triplets alone, at the head of a batch
     of 1023 and scattered through a batch of 1024 / 2500 give bit-identical T, R_t_2, R_t_3 and the same `iter` and status."""
     import torch
     from tft_vs_fund_amd import api

@@ -57,3 +57,25 @@ def test_ragged_entry_points_load_and_refuse_without_device():
     assert rc == -10001
     rc = lib.tff_pose_batch_ragged_dev(None, 0, None, None, 8, None, 0, 1, None, None, None, None, None, None)
     assert rc == -10001
+
+
+def test_pose_entry_points_refuse_a_null_context():
+    """Every `_dev`, `_host` and `_debug_dev` pose entry point answers a null context with TFF_E_INVALID ("null context"), whatever its route
+    selection would read from the context."""
+    from tft_vs_fund_amd.build import build_library
+    build_library()
+    lib = api.load_library()
+    x = np.zeros(64)
+    d = x.ctypes.data
+    called = 0
+    for stem in api.POSE_METHODS.values():
+        for suffix, extra in (("_dev", ()), ("_host", ()), ("_debug_dev", (d,))):
+            if stem + suffix not in api.EXPORTED_SYMBOLS or stem + suffix == "tff_pi_pose_batch_debug_dev":   # (its own signature: below)
+                continue
+            rc = getattr(lib, stem + suffix)(None, d, d, 0, 1, 8, d, d, d, None, None, None, *extra)
+            assert rc == -10001 and lib.tff_last_error() == b"null context", stem + suffix
+            called += 1
+    assert called == 8 + 8 + 5
+    for collinear in (0, 1):
+        assert lib.tff_pi_pose_batch_debug_dev(None, collinear, d, d, 0, 1, 8, d, d, d, None, None, None, None, None) == -10001
+        assert lib.tff_last_error() == b"null context"

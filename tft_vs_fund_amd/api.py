@@ -39,6 +39,7 @@ TFF_OPT_ROWS = 7
 TFF_OPT_DEBUG_FP_HANDOVER = 8
 TFF_OPT_DEBUG_ADAPTIVE = 9
 TFF_OPT_PRE = 10
+TFF_OPT_COUNT_ROWS = 11
 DEBUG_STRIDE = 128
 
 ST_OK, ST_TOO_FEW, ST_NONFINITE, ST_NO_POSE, ST_RANK, ST_NO_PARAM = 0, 1, 2, 3, 4, 5
@@ -231,7 +232,7 @@ class Context:
 
     def set_count_rows(self, on):
         """TFF_OPT_COUNT_ROWS: inlier counts with four hypotheses per wavefront (default) or one."""
-        _check(self.lib, self.lib.tff_ctx_set_option(self.handle, 11, int(bool(on))), "set_option")
+        _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_COUNT_ROWS, int(bool(on))), "set_option")
 
     def set_rows(self, on):
         """TFF_OPT_ROWS: "auto" / 2 (default) and True / 1 = the row kernels (four triplets per wavefront, one per row of 16 lanes) at any batch size:
@@ -259,7 +260,8 @@ class Context:
 
     def set_kernel_variant(self, v):
         """TFF_OPT_KERNEL.  Iterative TFT methods:
-        0 automatic (workgroup per triplet, fused single-wavefront kernel at small N), 1 fused always, 2 workgroup always."""
+        0 automatic (a workgroup per triplet at every N), 1 the fused single-wavefront kernels, 2 workgroup always (FaugPapa: the generic
+        block kernel instead of its own)."""
         _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_KERNEL, int(v)), "set_option")
 
     def set_stream(self, stream_ptr):
