@@ -21,7 +21,7 @@
  *   reconst  B x (3 x N) or NULL                                   (Reconst, 3xN)
  *   iter     B int32 or NULL  (0 for the linear methods, GH iterations otherwise)
  *   status   B int32 or NULL  (replaces MATLAB exceptions, see TFF_ST_*)
- * Ragged batches (tff_pose_batch_ragged_*, tff_repr_error_ragged_dev): triplets with different correspondence counts, packed:
+ * Ragged batches (tff_pose_batch_ragged_*): triplets with different correspondence counts, packed:
  *   offsets  B + 1 int64; triplet b owns correspondences offsets[b] .. offsets[b+1]-1, n_b = offsets[b+1] - offsets[b]
  *   corresp  correspondence n of triplet b = [x1 y1 x2 y2 x3 y3] at corresp[(offsets[b] + n)*6]
  *   reconst  3 doubles per correspondence at reconst[(offsets[b] + n)*3] or NULL;  calm, Rt2, Rt3, T, iter, status as above
@@ -298,6 +298,45 @@ int tff_linear_tft_pose_sampled_dev(tff_ctx* ctx, const double* scene, int32_t N
 int tff_linear_f_pose_sampled_dev(tff_ctx* ctx, const double* scene, int32_t Ns, const double* calm,
                                   const int32_t* sample_idx, int64_t B, int32_t n, double* Rt2, double* Rt3,
                                   double* T, int32_t* status);
+
+/* ---- matches with outliers: robust estimation over minimal samples of ONE scene (6 x Ns, shared CalM of 27 doubles) ------------------------------
+ * tff_sample_indices_dev: row b of sample_idx (B x n int32) = n DISTINCT indices in [0, Ns), a function of (seed, first + b, n, Ns) only -- stateless and
+ * counter-based, so any chunking or sharding of a hypothesis range draws the same samples.  1 <= n <= 16, Ns >= n, B >= 0, first >= 0 (else
+ * TFF_E_INVALID).  One thread per hypothesis, exactly n draws: a Fisher-Yates shuffle of which only the n swaps are kept.  With wrapping uint64 arithmetic
+ *     splitmix64(x): z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)
+ *     key = splitmix64(seed ^ ((first + b) * 0xD1342543DE82EF95))
+ *     for i in 0 .. n-1:  u = splitmix64(key + i) >> 32;  r = i + ((u * (Ns - i)) >> 32);  out[i] = look(r);  record (r, look(i))
+ *     look(p) = the value of the LAST record whose position is p, else p.            (numpy form: api.sample_indices_reference) */
+int tff_sample_indices_dev(tff_ctx* ctx, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, int32_t* sample_idx);
+
+/* Per-correspondence inlier flags of B pose hypotheses against the scene: mask (B x Ns, 0 / 1), counts (B, or NULL) = its row sums.  The rule and the
+ * arithmetic per correspondence are those of tff_inlier_count_batch_dev (one shared device function), so the row sums equal that function's counts. */
+int tff_inlier_mask_batch_dev(tff_ctx* ctx, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3,
+                              int64_t B, double threshold, uint8_t* mask, int32_t* counts);
+
+/* RANSAC with local optimisation; method = TFF_METHOD_LINEAR_TFT or TFF_METHOD_LINEAR_F (ids below).  The algorithm, from the public pieces:
+ *   1. idx = tff_sample_indices_dev(seed, 0, n_hyp, n_sample, Ns); hypotheses = the method's *_pose_sampled_dev on idx; count[h] = tff_inlier_count_batch_dev
+ *      at `threshold` (pixels, per coordinate).  n_sample = 0: the method's minimum (7 / 8); at most 16.
+ *   2. candidates: the n_cand hypotheses with status 0 that come first in the order (count descending, hypothesis index ascending); fewer successes, fewer
+ *      candidates.
+ *   3. lo_rounds times, for all candidates at once: each one's inlier mask -> its inliers in scene order, packed with device-side offsets -> ONE
+ *      tff_pose_batch_ragged_dev call of `method` (n_max = Ns) -> the refits' counts.  A candidate adopts its refit iff the refit's status is 0 and its count
+ *      is >= the candidate's: a fit to all of a pose's inliers is preferred to a minimal-sample pose of equal support, and a count never decreases.
+ *   4. the winner: the largest count, ties to the earlier candidate.  Rt2, Rt3 (12 each), T (27), mask (Ns flags of that pose; their sum is info[0]),
+ *      info = [inlier count, index of the hypothesis the winner started from, refits it adopted, number of candidates], status = TFF_ST_OK.
+ *      No successful hypothesis: status TFF_ST_NO_POSE, NaN in the three arrays, zero mask, info = [0, -1, 0, 0].
+ * The result is a function of the arguments (seed included) and the context's options only.  Hypotheses are processed in chunks of 262 144 (their pose records,
+ * 107 MB, the counts of all n_hyp hypotheses and K * Ns * 49 bytes for the refits are workspaces of the context); the result does not depend on the chunk size.
+ * _dev: device pointers, no host synchronisation and no device-to-host copy (selection, compaction and offsets are kernels).  _host: host pointers, one
+ * synchronisation.  Ns at most 2^24 (the ragged call's n_max).
+ * TFF_E_INVALID: another method, n_sample outside [minimum, 16], Ns < n_sample, n_hyp < 1 (or above 2^31 - 1), n_cand outside [1, 64], lo_rounds outside
+ * [0, 8], a threshold that is not a positive finite number, a null pointer, and what the ragged call refuses (TFF_OPT_ROWS = 0, TFF_OPT_KERNEL = 1). */
+int tff_robust_pose_dev(tff_ctx* ctx, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp,
+                        int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T,
+                        uint8_t* mask, int32_t* info, int32_t* status);
+int tff_robust_pose_host(tff_ctx* ctx, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp,
+                         int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T,
+                         uint8_t* mask, int32_t* info, int32_t* status);
 
 /* ---- multi-GPU (one process, one host thread + stream per device) ----------------------------------
  * The reference runs its triplets one after the other in one MATLAB thread (experiments.m:91-108); they are independent,

@@ -44,6 +44,7 @@ DEBUG_STRIDE = 128
 
 ST_OK, ST_TOO_FEW, ST_NONFINITE, ST_NO_POSE, ST_RANK, ST_NO_PARAM = 0, 1, 2, 3, 4, 5
 ST_BAD_OFFSETS = 6
+ROBUST_CHUNK = 262144        # hypotheses per chunk of tff_robust_pose_* (csrc/robust_kernel.h); the result does not depend on it
 
 _c_dp = ctypes.c_void_p
 _POSE_SIG = [ctypes.c_void_p, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -91,7 +92,7 @@ def load_library(path=None):
             if fn is not None:
                 fn.argtypes = _POSE_SIG + [_c_dp]
                 fn.restype = ctypes.c_int
-        V, I64, I32, F64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+        V, I64, I32, F64, U64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_uint64
         protos = {
             "tff_triangulate_batch_dev": [V, V, I64, V, I64, I32, I32, V],
             "tff_repr_error_batch_dev": [V, V, I64, V, I64, V, I64, I32, V],
@@ -112,6 +113,10 @@ def load_library(path=None):
             "tff_pose_batch_dev_multi": [V, I32, V, V, I64, I64, I32, V, V],
             "tff_pose_batch_ragged_dev": [V, I32, V, V, I32, V, I64, I64, V, V, V, V, V, V],
             "tff_pose_batch_ragged_host": [V, I32, V, V, V, I64, I64, V, V, V, V, V, V],
+            "tff_sample_indices_dev": [V, U64, I64, I64, I32, I32, V],
+            "tff_inlier_mask_batch_dev": [V, V, I32, V, V, V, I64, F64, V, V],
+            "tff_robust_pose_dev": [V, I32, V, I32, V, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
+            "tff_robust_pose_host": [V, I32, V, I32, V, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
         }
         for name, sig in protos.items():
             fn = getattr(lib, name)
@@ -154,6 +159,7 @@ EXPORTED_SYMBOLS = [
     "tff_rt_from_tft_batch_dev", "tff_linear_tft_batch_dev", "tff_linear_f_batch_dev", "tff_bundle_adjust_batch_dev", "tff_bundle_adjust_batch_host", "tff_bundle_adjust_views_batch_dev", "tff_bundle_adjust_views_batch_host", "tff_linear_tft_pose_sampled_dev", "tff_linear_f_pose_sampled_dev",
     "tff_multi_create", "tff_multi_destroy", "tff_multi_size", "tff_multi_ctx", "tff_multi_shard", "tff_pose_batch_host_multi", "tff_pose_batch_dev_multi",
     "tff_pose_batch_ragged_dev", "tff_pose_batch_ragged_host",
+    "tff_sample_indices_dev", "tff_inlier_mask_batch_dev", "tff_robust_pose_dev", "tff_robust_pose_host",
 ]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
@@ -163,6 +169,45 @@ METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "Nordbe
 
 # methods a ragged call (Context.pose_batch_ragged) supports
 RAGGED_METHODS = ("LinearTFTPoseEstimation", "LinearFPoseEstimation")
+
+
+# methods the robust estimator (Context.robust_pose) draws its hypotheses and refits with, and their minimal sample
+ROBUST_METHODS = {"LinearTFTPoseEstimation": 7, "LinearFPoseEstimation": 8}
+
+
+def _splitmix64(x):
+    z = x + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def sample_indices_reference(seed, first, B, n, Ns):
+    """What tff_sample_indices_dev computes (include/tftfund.h), in numpy: (B, n) int32, row b = n distinct indices in [0, Ns), a function of
+    (seed, first + b, n, Ns) only.  A Fisher-Yates shuffle of the virtual array 0 .. Ns-1 of which only the n swaps are kept; wrapping uint64."""
+    if not (1 <= n <= 16 and Ns >= n and B >= 0 and first >= 0):
+        raise ValueError("need 1 <= n <= 16, Ns >= n, B >= 0, first >= 0")
+    with np.errstate(over="ignore"):
+        h = np.uint64(first) + np.arange(B, dtype=np.uint64)
+        key = _splitmix64(np.uint64(seed) ^ (h * np.uint64(0xD1342543DE82EF95)))
+        out = np.empty((B, n), dtype=np.int32)
+        pos = np.empty((B, n), dtype=np.int64)
+        val = np.empty((B, n), dtype=np.int64)
+
+        def look(p, m):                      # the value of the LAST of the first m records whose position is p, else p
+            v = p.copy()
+            for j in range(m):
+                v = np.where(pos[:, j] == p, val[:, j], v)
+            return v
+
+        for i in range(n):
+            u = _splitmix64(key + np.uint64(i)) >> np.uint64(32)
+            r = (np.uint64(i) + ((u * np.uint64(Ns - i)) >> np.uint64(32))).astype(np.int64)
+            vr, vi = look(r, i), look(np.full(B, i, dtype=np.int64), i)
+            out[:, i] = vr
+            pos[:, i] = r
+            val[:, i] = vi
+    return out
 
 
 def pack_ragged(items):
@@ -599,6 +644,82 @@ class Context:
                             self._p(st)), "pose_sampled")
         return dict(R_t_2=Rt2.reshape(B, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(B, 4, 3).transpose(1, 2),
                     T=T.reshape(B, 3, 3, 3).permute(0, 3, 2, 1), status=st, _raw=(Rt2, Rt3, T))
+
+    # ---- matches with outliers ------------------------------------------------------------------------
+    def sample_indices(self, seed, first, B, n, Ns):
+        """tff_sample_indices_dev: (B, n) int32 CUDA tensor, row b = the n distinct indices of hypothesis first + b (see sample_indices_reference)."""
+        self._begin()
+        out = torch.empty((max(int(B), 0), max(int(n), 0)), dtype=torch.int32, device=torch.device("cuda", self.device))
+        _check(self.lib, self.lib.tff_sample_indices_dev(self.handle, int(seed), int(first), int(B), int(n), int(Ns), self._p(out)),
+               "tff_sample_indices_dev")
+        return out
+
+    def inlier_mask(self, scene, calm, R_t_2, R_t_3, threshold, with_counts=False):
+        """Inlier flags (B, Ns) uint8 of B pose hypotheses against one scene (Ns, 6), by the rule of inlier_count: the row sums are its counts."""
+        self._begin()
+        scene = self._t(scene); Ns = scene.shape[0]
+        calm = self._t(calm).t().contiguous().reshape(27)
+        r2 = self._cams_cm(self._t(R_t_2)); r3 = self._cams_cm(self._t(R_t_3)); B = r2.shape[0]
+        mask = torch.empty((B, Ns), dtype=torch.uint8, device=scene.device)
+        cnt = torch.empty(B, dtype=torch.int32, device=scene.device) if with_counts else None
+        _check(self.lib, self.lib.tff_inlier_mask_batch_dev(self.handle, self._p(scene), Ns, self._p(calm), self._p(r2), self._p(r3), B,
+                                                            float(threshold), self._p(mask), self._p(cnt)), "tff_inlier_mask_batch_dev")
+        return (mask, cnt) if with_counts else mask
+
+    def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None):
+        """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
+        best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
+        Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
+        -> CUDA tensors (0-d for the five scalars) and no synchronisation; numpy in -> numpy / ints (the _host form).  refine = a name in POSE_METHODS:
+        that method once on the final inliers through pose_batch (reads the count on the host), as R_t_2_refined, R_t_3_refined, T_refined,
+        iter_refined, status_refined."""
+        if method not in ROBUST_METHODS:
+            raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
+        if refine is not None and refine not in POSE_METHODS:
+            raise ValueError("unknown refine method %r" % (refine,))
+        mid = METHOD_IDS[method]
+        ns = 0 if n_sample is None else int(n_sample)
+        args = (int(seed), int(n_hyp), ns, float(threshold), int(candidates), int(lo_rounds))
+        if isinstance(scene, np.ndarray):
+            sc = np.ascontiguousarray(scene, dtype=np.float64)
+            if sc.ndim != 2 or sc.shape[1] != 6:
+                raise ValueError("scene must be (Ns, 6)")
+            Ns = sc.shape[0]
+            calm_cm, _ = self._calm_cm_np(calm, 1)
+            Rt2 = np.empty(12); Rt3 = np.empty(12); T = np.empty(27)
+            mask = np.zeros(Ns, dtype=np.uint8); info = np.zeros(4, dtype=np.int32); st = np.zeros(1, dtype=np.int32)
+            ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+            _check(self.lib, self.lib.tff_robust_pose_host(self.handle, mid, ptr(sc), Ns, ptr(calm_cm), *args, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask),
+                                                           ptr(info), ptr(st)), "tff_robust_pose_host")
+            out = dict(R_t_2=Rt2.reshape(4, 3).T, R_t_3=Rt3.reshape(4, 3).T, T=T.reshape(3, 3, 3).transpose(2, 1, 0), mask=mask,
+                       inliers=int(info[0]), hypothesis=int(info[1]), refits=int(info[2]), candidates=int(info[3]), status=int(st[0]))
+            inl = sc[mask != 0]
+        else:
+            if not (scene.is_cuda and scene.dtype == torch.float64 and scene.is_contiguous() and scene.dim() == 2 and scene.shape[1] == 6):
+                raise ValueError("scene must be a contiguous float64 CUDA tensor of shape (Ns, 6)")
+            dev = scene.device
+            Ns = scene.shape[0]
+            if isinstance(calm, np.ndarray):
+                calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
+            if tuple(calm.shape) != (9, 3):
+                raise ValueError("CalM must be (9, 3)")
+            calm = calm.to(device=dev, dtype=torch.float64)
+            calm_cm = calm.t().contiguous().reshape(27)
+            Rt2 = torch.empty(12, dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
+            T = torch.empty(27, dtype=torch.float64, device=dev)
+            mask = torch.empty(Ns, dtype=torch.uint8, device=dev)
+            info = torch.empty(4, dtype=torch.int32, device=dev); st = torch.empty(1, dtype=torch.int32, device=dev)
+            self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            _check(self.lib, self.lib.tff_robust_pose_dev(self.handle, mid, self._p(scene), Ns, self._p(calm_cm), *args, self._p(Rt2), self._p(Rt3),
+                                                          self._p(T), self._p(mask), self._p(info), self._p(st)), "tff_robust_pose_dev")
+            out = dict(R_t_2=Rt2.reshape(4, 3).t(), R_t_3=Rt3.reshape(4, 3).t(), T=T.reshape(3, 3, 3).permute(2, 1, 0), mask=mask,
+                       inliers=info[0], hypothesis=info[1], refits=info[2], candidates=info[3], status=st[0])
+            inl = scene[mask != 0].contiguous() if refine is not None else None   # (boolean indexing reads the count on the host)
+        if refine is not None:
+            r = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
+            out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
+                       status_refined=r["status"][0])
+        return out
 
 
 class MultiContext:

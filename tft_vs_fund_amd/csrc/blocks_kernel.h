@@ -93,6 +93,39 @@ __device__ __forceinline__ bool certainly_positive_definite(const double (&S)[4]
     }
     return pd;
 }
+// ---- the inlier rule for one correspondence: k_inlier_count_staged, k_inlier_count_rows and k_inlier_mask (robust_kernel.h) share count_if_inlier; k_repr_error,
+// which also serves ReprError (given points, the RMS sum), keeps its own loop and shares the threshold form.  count_if_inlier adds to a counter instead of returning
+// a flag: the count kernels' loops keep the shape, and the instructions, they had when each spelled the rule out ----
+// Z of the certain-outlier test at threshold thr (lower triangle): thr^2 * 2 sum_v P_v(3,:)' P_v(3,:)
+__device__ __forceinline__ void inlier_threshold_form(const double (&P)[3][12], const double thr, double (&Zt)[4][4]) {
+    const double k2 = 2.0 * thr * thr;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) Zt[i][j] = k2 * (P[0][8 + i] * P[0][8 + j] + P[1][8 + i] * P[1][8 + j] + P[2][8 + i] * P[2][8 + j]);
+}
+// the whole rule, counts only: certain-outlier pivot test, then the certified DLT ladder, then the six comparisons; cnt += 1 for an inlier.  P: the
+// three cameras in registers, cam0 .. cam2: the same cameras in LDS (row-major 3 x 4), Zt: inlier_threshold_form(P, thr)
+__device__ __forceinline__ void count_if_inlier(const double (&P)[3][12], const double (&Zt)[4][4], const double* cam0, const double* cam1,
+                                                const double* cam2, const Pt6& p, const double thr, int& cnt) {
+    double S[4][4], X[4];
+    tri_zero(S);
+    tri_accum(S, P[0], p.v[0], p.v[1]);
+    tri_accum(S, P[1], p.v[2], p.v[3]);
+    tri_accum(S, P[2], p.v[4], p.v[5]);
+    if (certainly_positive_definite(S, Zt)) return;
+    dlt_point_solve<true, true>(S, cam0, cam1, cam2, true, p.v[0], p.v[1], p.v[2], p.v[3], p.v[4], p.v[5], X);
+    bool in = true;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const double u = P[v][0] * X[0] + P[v][1] * X[1] + P[v][2] * X[2] + P[v][3] * X[3];
+        const double w2 = P[v][4] * X[0] + P[v][5] * X[1] + P[v][6] * X[2] + P[v][7] * X[3];
+        const double z = P[v][8] * X[0] + P[v][9] * X[1] + P[v][10] * X[2] + P[v][11] * X[3];
+        const double dx = u / z - p.v[2 * v], dy = w2 / z - p.v[2 * v + 1];
+        in = in && (fabs(dx) <= thr) && (fabs(dy) <= thr);                  // sum(abs(residuals) > th, 1) == 0
+    }
+    cnt += in ? 1 : 0;
+}
 __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
     __shared__ double cam[3][12];
     const int lane = lane_id();
@@ -123,13 +156,7 @@ __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
         // (divergent, gap-dependent) eigen-solves are left to the correspondences that could be inliers.
         const bool count_only = a.inliers && !a.err && !a.pts3d;
         double Zt[4][4];
-        if (count_only) {
-            const double k2 = 2.0 * a.thr * a.thr;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j <= i; ++j) Zt[i][j] = k2 * (P[0][8 + i] * P[0][8 + j] + P[1][8 + i] * P[1][8 + j] + P[2][8 + i] * P[2][8 + j]);
-        }
+        if (count_only) inlier_threshold_form(P, a.thr, Zt);
         double ss = 0.0;
         int cnt = 0;
 #pragma unroll 1
@@ -204,32 +231,11 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 4) k_inlier_count_staged
         load_uniform12(camw + 12, P[1]);
         load_uniform12(camw + 24, P[2]);
         double Zt[4][4];
-        const double k2 = 2.0 * a.thr * a.thr;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) Zt[i][j] = k2 * (P[0][8 + i] * P[0][8 + j] + P[1][8 + i] * P[1][8 + j] + P[2][8 + i] * P[2][8 + j]);
+        inlier_threshold_form(P, a.thr, Zt);
         int cnt = 0;
 #pragma unroll 1
         for (int i = lane; i < a.N; i += WAVE) {
-            const Pt6 p = load_pt(scene, i);
-            double S[4][4], X[4];
-            tri_zero(S);
-            tri_accum(S, P[0], p.v[0], p.v[1]);
-            tri_accum(S, P[1], p.v[2], p.v[3]);
-            tri_accum(S, P[2], p.v[4], p.v[5]);
-            if (certainly_positive_definite(S, Zt)) continue;
-            dlt_point_solve<true, true>(S, camw, camw + 12, camw + 24, true, p.v[0], p.v[1], p.v[2], p.v[3], p.v[4], p.v[5], X);
-            bool in = true;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const double u = P[v][0] * X[0] + P[v][1] * X[1] + P[v][2] * X[2] + P[v][3] * X[3];
-                const double w2 = P[v][4] * X[0] + P[v][5] * X[1] + P[v][6] * X[2] + P[v][7] * X[3];
-                const double z = P[v][8] * X[0] + P[v][9] * X[1] + P[v][10] * X[2] + P[v][11] * X[3];
-                const double dx = u / z - p.v[2 * v], dy = w2 / z - p.v[2 * v + 1];
-                in = in && (fabs(dx) <= a.thr) && (fabs(dy) <= a.thr);     // sum(abs(residuals) > th, 1) == 0
-            }
-            cnt += in ? 1 : 0;
+            count_if_inlier(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, cnt);
         }
         cnt = wave_sum_i(cnt);
         if (lane == 0) a.inliers[b] = cnt;
@@ -273,32 +279,11 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_rows(c
 #pragma unroll
             for (int c = 0; c < 12; ++c) P[v][c] = camw[12 * v + c];
         double Zt[4][4];
-        const double k2 = 2.0 * a.thr * a.thr;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) Zt[i][j] = k2 * (P[0][8 + i] * P[0][8 + j] + P[1][8 + i] * P[1][8 + j] + P[2][8 + i] * P[2][8 + j]);
+        inlier_threshold_form(P, a.thr, Zt);
         int cnt = 0;
 #pragma unroll 1
         for (int i = p; i < a.N; i += 16) {
-            const Pt6 q = load_pt(scene, i);
-            double S[4][4], X[4];
-            tri_zero(S);
-            tri_accum(S, P[0], q.v[0], q.v[1]);
-            tri_accum(S, P[1], q.v[2], q.v[3]);
-            tri_accum(S, P[2], q.v[4], q.v[5]);
-            if (certainly_positive_definite(S, Zt)) continue;
-            dlt_point_solve<true, true>(S, camw, camw + 12, camw + 24, true, q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], X);
-            bool in = true;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const double u = P[v][0] * X[0] + P[v][1] * X[1] + P[v][2] * X[2] + P[v][3] * X[3];
-                const double w2 = P[v][4] * X[0] + P[v][5] * X[1] + P[v][6] * X[2] + P[v][7] * X[3];
-                const double z = P[v][8] * X[0] + P[v][9] * X[1] + P[v][10] * X[2] + P[v][11] * X[3];
-                const double dx = u / z - q.v[2 * v], dy = w2 / z - q.v[2 * v + 1];
-                in = in && (fabs(dx) <= a.thr) && (fabs(dy) <= a.thr);     // sum(abs(residuals) > th, 1) == 0
-            }
-            cnt += in ? 1 : 0;
+            count_if_inlier(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, cnt);
         }
         const double tot = row_sum16((double)cnt);
         if (p == 0 && valid) a.inliers[b] = (int)tot;

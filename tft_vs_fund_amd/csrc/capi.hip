@@ -16,6 +16,7 @@
 #include "../../include/tftfund.h"
 #include "launch.h"
 #include "ragged_kernel.h"
+#include "robust_kernel.h"
 
 namespace {
 
@@ -71,6 +72,7 @@ struct tff_ctx {
     int stage = -1;
     DevBuf in, calm, out, idx, scratch_status, gh_rec, gh_topt, gh_init, spill, pre_rec, retry;
     DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
+    DevBuf robust_hyp, robust_counts, robust_cand;   // tff_robust_pose_*: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust)
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
     int spill_only_if_needed = 0;          // TFF_OPT_SPILL
@@ -549,6 +551,14 @@ int pose_host(tff_ctx* c, int32_t method, PoseCall h) {
 // LDS staging decision per triplet.  No host synchronisation: the plan's counts stay on the device.
 constexpr int32_t RAGGED_MAX_N = 1 << 24;   // bounds the plan's buckets (n_max + 1 of them)
 
+// the ragged chain of a known method under the context's options, or the refusal (the robust estimator's refits come through here too)
+int ragged_route(const tff_ctx* c, int32_t method, const RaggedRoute** route) {
+    if (!use_rows(c)) return fail(TFF_E_INVALID, "ragged batches run on the row kernels: TFF_OPT_ROWS = 0 is not supported");
+    if (c->kernel_variant == 1) return fail(TFF_E_INVALID, "ragged batches: TFF_OPT_KERNEL = 1 (fused single-wavefront kernels) is not supported");
+    *route = &method_of(method)->ragged;
+    if (!(*route)->fast) return fail(TFF_E_INVALID, "ragged batches are implemented for LinearTFT and LinearF only; group this method's triplets by N");
+    return 0;
+}
 int check_ragged(const tff_ctx* c, int32_t method, const PoseCall& p, const RaggedRoute** route) {
     if (!method_of(method)) return fail(TFF_E_INVALID, "unknown method");
     if (p.B < 0 || p.N < 0) return fail(TFF_E_INVALID, "negative batch size or n_max");
@@ -557,11 +567,7 @@ int check_ragged(const tff_ctx* c, int32_t method, const PoseCall& p, const Ragg
     if (!p.offsets) return fail(TFF_E_INVALID, "null offsets");
     if (p.B > 0 && (!p.corresp || !p.calm)) return fail(TFF_E_INVALID, "null input pointer");
     if (p.calm_stride != 0 && p.calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
-    if (!use_rows(c)) return fail(TFF_E_INVALID, "ragged batches run on the row kernels: TFF_OPT_ROWS = 0 is not supported");
-    if (c->kernel_variant == 1) return fail(TFF_E_INVALID, "ragged batches: TFF_OPT_KERNEL = 1 (fused single-wavefront kernels) is not supported");
-    *route = &method_of(method)->ragged;
-    if (!(*route)->fast) return fail(TFF_E_INVALID, "ragged batches are implemented for LinearTFT and LinearF only; group this method's triplets by N");
-    return 0;
+    return ragged_route(c, method, route);
 }
 
 // largest n <= n_max whose fixed-N call stages the correspondences of the fix-up kernel in LDS (launch_pose_rows), -1 if none: the rule holds
@@ -614,11 +620,137 @@ int launch_ragged(tff_ctx* c, const RaggedRoute& r, const PoseCall& p) {
     return launch_retry_fixup(c, r.fixup, lds, a);
 }
 
+// ---- inlier counts and flags of pose hypotheses against one shared scene ------------------------------------------------------------------------
+int launch_inlier_count(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B, double threshold,
+                        int32_t* counts, double* err) {
+    tff::ReprErrorArgs a{nullptr, 0, calm, Rt2, Rt3, scene, 0, nullptr, (long)B, Ns, threshold, err, counts};
+    const size_t staged = ((size_t)6 * Ns + 36 * tff::INLIER_WG_WAVES) * sizeof(double);
+    if (err || staged > 48 * 1024 || B < 4096) return launch(c, tff::k_repr_error, tff::pose_grid(B), 64, 0, a);
+    // counts only, many hypotheses, a scene that fits the LDS a few times over: stage it once per workgroup (blocks_kernel.h)
+    if (c->count_rows) {                                                 // four hypotheses per wavefront (blocks_kernel.h::k_inlier_count_rows): two workgroups per CU
+        const size_t staged_rows = ((size_t)6 * Ns + 36 * 4 * tff::INLIER_WG_WAVES) * sizeof(double);
+        long grid_rows = 256L * 2;
+        const long per_wg = 4L * tff::INLIER_WG_WAVES;
+        if (grid_rows * per_wg > B) grid_rows = (B + per_wg - 1) / per_wg;
+        return launch(c, tff::k_inlier_count_rows, (unsigned)grid_rows, 64 * tff::INLIER_WG_WAVES, staged_rows, a);
+    }
+    const int per_cu = (int)((LDS_LIMIT / (staged + 512) < 4) ? LDS_LIMIT / (staged + 512) : 4);
+    long grid = 256L * per_cu;
+    if (grid * tff::INLIER_WG_WAVES > B) grid = (B + tff::INLIER_WG_WAVES - 1) / tff::INLIER_WG_WAVES;
+    return launch(c, tff::k_inlier_count_staged, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, staged, a);
+}
+// one wavefront per hypothesis (robust_kernel.h::k_inlier_mask); gate: see InlierMaskArgs
+int launch_inlier_mask(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B, double threshold,
+                       uint8_t* mask, int32_t* counts, const int32_t* gate) {
+    tff::InlierMaskArgs a{scene, calm, Rt2, Rt3, (long)B, Ns, threshold, mask, counts, gate};
+    return launch(c, tff::k_inlier_mask, tff::pose_grid(B), 64, 0, a);
+}
+int launch_sample_indices(tff_ctx* c, uint64_t seed, int64_t first, const unsigned long long* keys, int64_t B, int32_t n, int32_t Ns, int32_t* out) {
+    tff::SampleArgs a{(unsigned long long)seed, (long)first, keys, (long)B, n, Ns, out};
+    return launch(c, tff::k_sample_indices, (unsigned)((B + 255) / 256), 256, 0, a);
+}
+
+// ---- robust estimation (tff_robust_pose_*; kernels and the chunking in robust_kernel.h) ------------------------------------------------------------
+struct RobustCall {
+    int32_t method; const double* scene; int32_t Ns; const double* calm; uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold;
+    int32_t n_cand; int32_t lo_rounds;
+    double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
+};
+int32_t robust_min_sample(int32_t method) { return method == TFF_METHOD_LINEAR_F ? 8 : 7; }
+// argument checks shared by the two forms; n_sample = 0 becomes the method's minimum; *route: the method's ragged chain (the refit)
+int check_robust(const tff_ctx* c, RobustCall* q, const RaggedRoute** route) {
+    if (q->method != TFF_METHOD_LINEAR_TFT && q->method != TFF_METHOD_LINEAR_F)
+        return fail(TFF_E_INVALID, "robust estimation: the method must be TFF_METHOD_LINEAR_TFT or TFF_METHOD_LINEAR_F");
+    const int32_t least = robust_min_sample(q->method);
+    if (q->n_sample == 0) q->n_sample = least;
+    if (q->n_sample < least || q->n_sample > tff::ROBUST_MAX_SAMPLE) return fail(TFF_E_INVALID, "robust estimation: n_sample must be 0 or between the method's minimum (7 / 8) and 16");
+    if (q->Ns < q->n_sample) return fail(TFF_E_INVALID, "robust estimation: fewer correspondences than one sample");
+    if (q->n_hyp < 1 || q->n_hyp > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_hyp must be between 1 and 2^31 - 1");
+    if (q->n_cand < 1 || q->n_cand > tff::ROBUST_MAX_CAND) return fail(TFF_E_INVALID, "robust estimation: n_cand must be between 1 and 64");
+    if (q->lo_rounds < 0 || q->lo_rounds > 8) return fail(TFF_E_INVALID, "robust estimation: lo_rounds must be between 0 and 8");
+    if (!(q->threshold > 0.0) || !(q->threshold <= 1.79769313486231570e308)) return fail(TFF_E_INVALID, "robust estimation: the threshold must be a positive finite number");
+    if (!q->scene || !q->calm || !q->Rt2 || !q->Rt3 || !q->T || !q->mask || !q->info || !q->status) return fail(TFF_E_INVALID, "null pointer");
+    if (q->Ns > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: more than 2^24 correspondences");
+    return ragged_route(c, q->method, route);                                // the refit's refusals: TFF_OPT_ROWS = 0, TFF_OPT_KERNEL = 1
+}
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// device pointers; the lock is held and the context's device current
+int launch_robust(tff_ctx* c, const RaggedRoute& route, const RobustCall& q) {
+    const Method& m = METHODS[q.method];
+    const int K = q.n_cand, Ns = q.Ns, n = q.n_sample;
+    const int64_t chunk = q.n_hyp < tff::ROBUST_CHUNK ? q.n_hyp : tff::ROBUST_CHUNK;
+    // workspaces.  One chunk of hypotheses: poses (51 doubles) | status | sample indices
+    TFF_TRY(c->robust_hyp.reserve(align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * sizeof(int32_t)) + (size_t)chunk * n * sizeof(int32_t)));
+    TFF_TRY(c->robust_counts.reserve((size_t)q.n_hyp * sizeof(int32_t)));
+    char* hp = (char*)c->robust_hyp.p;
+    double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
+    int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
+    int32_t* h_idx = (int32_t*)hp;
+    int32_t* counts = (int32_t*)c->robust_counts.p;
+    // the candidates: keys | poses | refits | offsets | seven int arrays of K | sample indices | masks | the packed refit batch
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    const size_t o_sel = carve((size_t)K * 8), o_pose = carve((size_t)K * 51 * 8), o_ref = carve((size_t)K * 51 * 8), o_off = carve((size_t)(K + 1) * 8),
+                 o_int = carve((size_t)K * 7 * 4), o_idx = carve((size_t)K * n * 4), o_mask = carve((size_t)K * Ns), o_pack = carve((size_t)K * Ns * 6 * 8);
+    TFF_TRY(c->robust_cand.reserve(off));
+    char* cp = (char*)c->robust_cand.p;
+    unsigned long long* sel = (unsigned long long*)(cp + o_sel);
+    int32_t* ints = (int32_t*)(cp + o_int);
+    tff::RobustState s{};
+    s.sel = sel; s.K = K; s.Ns = Ns;
+    s.cnt = ints; s.seed_idx = ints + K; s.nref = ints + 2 * K; s.status = ints + 3 * K; s.ref_status = ints + 4 * K; s.ref_cnt = ints + 5 * K;
+    int32_t* mask_cnt = ints + 6 * K;
+    s.mask_cnt = mask_cnt;
+    s.pose = (double*)(cp + o_pose); s.ref_pose = (double*)(cp + o_ref);
+    s.offsets = (long*)(cp + o_off);
+    uint8_t* masks = (uint8_t*)(cp + o_mask);
+    s.mask = masks;
+    s.scene = q.scene; s.packed = (double*)(cp + o_pack);
+    int32_t* c_idx = (int32_t*)(cp + o_idx);
+
+    auto sampled = [&](const int32_t* idx, int64_t B, double* pose, int32_t* status) {   // the method's *_pose_sampled_dev on device records [Rt2 | Rt3 | T]
+        PoseCall p{q.scene, q.calm, 0, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
+        p.sample_idx = idx; p.sample_ns = Ns;
+        return m.launch(c, p);
+    };
+    // 1. hypotheses and their counts, chunk by chunk
+    for (int64_t first = 0; first < q.n_hyp; first += chunk) {
+        const int64_t B = q.n_hyp - first < chunk ? q.n_hyp - first : chunk;
+        TFF_TRY(launch_sample_indices(c, q.seed, first, nullptr, B, n, Ns, h_idx));
+        TFF_TRY(sampled(h_idx, B, h_pose, h_status));
+        TFF_TRY(launch_inlier_count(c, q.scene, Ns, q.calm, h_pose, h_pose + B * 12, B, q.threshold, counts + first, nullptr));
+        TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{counts + first, h_status, (long)B}));
+    }
+    // 2. the K best successes in the order (count descending, index ascending), then their poses again from their indices
+    TFF_HIP(hipMemsetAsync(sel, 0, (size_t)K * 8, c->stream));
+    const long topk_blocks = (q.n_hyp + tff::ROBUST_TOPK_THREADS - 1) / tff::ROBUST_TOPK_THREADS;
+    for (int r = 0; r < K; ++r)
+        TFF_TRY(launch(c, tff::k_robust_topk, (unsigned)(topk_blocks < 1024 ? topk_blocks : 1024), tff::ROBUST_TOPK_THREADS, 0, tff::RobustTopkArgs{counts, (long)q.n_hyp, sel, r}));
+    TFF_TRY(launch_sample_indices(c, q.seed, 0, sel, K, n, Ns, c_idx));
+    TFF_TRY(sampled(c_idx, K, s.pose, s.status));
+    TFF_TRY(launch(c, tff::k_robust_seed, 1, 64, 0, s));
+    // 3. local optimisation, all candidates at once: masks -> packed inliers -> one ragged refit -> counts -> adopt
+    for (int round = 0; round < q.lo_rounds; ++round) {
+        TFF_TRY(launch_inlier_mask(c, q.scene, Ns, q.calm, s.pose, s.pose + K * 12, K, q.threshold, masks, mask_cnt, nullptr));
+        TFF_TRY(launch(c, tff::k_robust_offsets, 1, 64, 0, s));
+        TFF_TRY(launch(c, tff::k_robust_compact, (unsigned)K, tff::ROBUST_COMPACT_THREADS, 0, s));
+        PoseCall p{s.packed, q.calm, 0, K, Ns, s.ref_pose, s.ref_pose + K * 12, s.ref_pose + K * 24, nullptr, nullptr, s.ref_status, nullptr};
+        p.offsets = (const int64_t*)s.offsets;
+        TFF_TRY(launch_ragged(c, route, p));
+        TFF_TRY(launch_inlier_count(c, q.scene, Ns, q.calm, s.ref_pose, s.ref_pose + K * 12, K, q.threshold, s.ref_cnt, nullptr));
+        TFF_TRY(launch(c, tff::k_robust_adopt, (unsigned)K, 64, 0, s));
+    }
+    // 4. the winner and the mask of its pose (skipped, the mask staying zero, when there is none)
+    TFF_TRY(launch(c, tff::k_robust_finish, 1, 64, 0, tff::RobustFinishArgs{s, q.Rt2, q.Rt3, q.T, q.info, q.status}));
+    TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)Ns, c->stream));
+    return launch_inlier_mask(c, q.scene, Ns, q.calm, q.Rt2, q.Rt3, 1, q.threshold, q.mask, q.info, q.status);
+}
+
 }  // namespace
 
 extern "C" {
 
-int tff_version(void) { return 101; }
+int tff_version(void) { return 102; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -643,7 +775,8 @@ void tff_ctx_destroy(tff_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
-    for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off})
+    for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
+                      &c->robust_cand})
         b->release();
     delete c;
 }
@@ -793,6 +926,64 @@ int tff_pose_batch_ragged_host(tff_ctx* c, int32_t method, const double* corresp
     });
 }
 
+// ---- matches with outliers: sampler, inlier flags, the robust estimator ------------------------------------------------------------------------
+int tff_sample_indices_dev(tff_ctx* c, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, int32_t* sample_idx) {
+    TFF_ENTER(c);
+    if (n < 1 || n > tff::ROBUST_MAX_SAMPLE || Ns < n || B < 0 || first < 0) return fail(TFF_E_INVALID, "sample_indices: need 1 <= n <= 16, Ns >= n, B >= 0, first >= 0");
+    return run_batch(c, B, sample_idx != nullptr, "null pointer", nullptr, [&] { return launch_sample_indices(c, seed, first, nullptr, B, n, Ns, sample_idx); });
+}
+
+int tff_inlier_mask_batch_dev(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B,
+                              double threshold, uint8_t* mask, int32_t* counts) {
+    TFF_ENTER(c);
+    if (B < 0 || Ns < 0) return fail(TFF_E_INVALID, "negative size");
+    return run_batch(c, B, scene && calm && Rt2 && Rt3 && mask, "null pointer", nullptr,
+                     [&] { return launch_inlier_mask(c, scene, Ns, calm, Rt2, Rt3, B, threshold, mask, counts, nullptr); });
+}
+
+int tff_robust_pose_dev(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
+                        double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
+                        int32_t* status) {
+    TFF_ENTER(c);
+    RobustCall q{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_robust(c, &q, &route));
+    TFF_HIP(hipSetDevice(c->device));
+    return launch_robust(c, *route, q);
+}
+
+// host pointers: H2D of the scene and CalM, the _dev path, D2H of the outputs, one synchronisation
+int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
+                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
+                         int32_t* status) {
+    TFF_ENTER(c);
+    RobustCall h{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_robust(c, &h, &route));
+    TFF_HIP(hipSetDevice(c->device));
+    const size_t nscene = (size_t)Ns * 6 * sizeof(double);
+    TFF_TRY(c->in.reserve(nscene));
+    TFF_TRY(c->calm.reserve(27 * sizeof(double)));
+    TFF_TRY(c->out.reserve(51 * sizeof(double) + (size_t)Ns));
+    TFF_TRY(c->idx.reserve(5 * sizeof(int32_t)));
+    RobustCall d = h;
+    d.scene = (const double*)c->in.p; d.calm = (const double*)c->calm.p;
+    d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + 12; d.T = d.Rt3 + 12; d.mask = (uint8_t*)(d.T + 27);
+    d.info = (int32_t*)c->idx.p; d.status = d.info + 4;
+    TFF_HIP(hipMemcpyAsync(c->in.p, scene, nscene, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(c->calm.p, calm, 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TFF_TRY(launch_robust(c, *route, d));
+    TFF_HIP(hipMemcpyAsync(Rt2, d.Rt2, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(Rt3, d.Rt3, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(T, d.T, 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(mask, d.mask, (size_t)Ns, hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(info, d.info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(status, d.status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+
 // ---------------------------------------------------------------------------------------------
 // Building blocks (device pointers only)
 // ---------------------------------------------------------------------------------------------
@@ -823,23 +1014,8 @@ int tff_inlier_count_batch_dev(tff_ctx* c, const double* scene, int32_t Ns, cons
                                int64_t B, double threshold, int32_t* counts, double* err) {
     TFF_ENTER(c);
     if (B < 0 || Ns < 0) return fail(TFF_E_INVALID, "negative size");
-    return run_batch(c, B, scene && calm && Rt2 && Rt3 && counts, "null pointer", nullptr, [&] {
-        tff::ReprErrorArgs a{nullptr, 0, calm, Rt2, Rt3, scene, 0, nullptr, (long)B, Ns, threshold, err, counts};
-        const size_t staged = ((size_t)6 * Ns + 36 * tff::INLIER_WG_WAVES) * sizeof(double);
-        if (err || staged > 48 * 1024 || B < 4096) return launch(c, tff::k_repr_error, tff::pose_grid(B), 64, 0, a);
-        // counts only, many hypotheses, a scene that fits the LDS a few times over: stage it once per workgroup (blocks_kernel.h)
-        if (c->count_rows) {                                                 // four hypotheses per wavefront (blocks_kernel.h::k_inlier_count_rows): two workgroups per CU
-            const size_t staged_rows = ((size_t)6 * Ns + 36 * 4 * tff::INLIER_WG_WAVES) * sizeof(double);
-            long grid_rows = 256L * 2;
-            const long per_wg = 4L * tff::INLIER_WG_WAVES;
-            if (grid_rows * per_wg > B) grid_rows = (B + per_wg - 1) / per_wg;
-            return launch(c, tff::k_inlier_count_rows, (unsigned)grid_rows, 64 * tff::INLIER_WG_WAVES, staged_rows, a);
-        }
-        const int per_cu = (int)((LDS_LIMIT / (staged + 512) < 4) ? LDS_LIMIT / (staged + 512) : 4);
-        long grid = 256L * per_cu;
-        if (grid * tff::INLIER_WG_WAVES > B) grid = (B + tff::INLIER_WG_WAVES - 1) / tff::INLIER_WG_WAVES;
-        return launch(c, tff::k_inlier_count_staged, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, staged, a);
-    });
+    return run_batch(c, B, scene && calm && Rt2 && Rt3 && counts, "null pointer", nullptr,
+                     [&] { return launch_inlier_count(c, scene, Ns, calm, Rt2, Rt3, B, threshold, counts, err); });
 }
 
 int tff_transform_tft_batch_dev(tff_ctx* c, const double* T, const double* M1, const double* M2, const double* M3, int64_t m_stride,
