@@ -338,6 +338,36 @@ int tff_robust_pose_host(tff_ctx* ctx, int32_t method, const double* scene, int3
                          int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T,
                          uint8_t* mask, int32_t* info, int32_t* status);
 
+/* ---- robust estimation for a batch of scenes in one call: the triplet lists of a dataset (experiments_real.m) ----------------------------------------------
+ * scenes: packed 6 x n_total doubles as in tff_pose_batch_ragged_*; scene_offsets: S + 1 int64 (on the device for _dev), scene s owns the correspondences
+ * scene_offsets[s] .. scene_offsets[s+1]-1, n_s of them.  n_total (host, at most 2^31 - 1) bounds every offset and sizes `mask` and the workspaces; ns_max
+ * (host, at most 2^24) bounds every n_s and is the refit's n_max.  calm: 27 doubles shared (calm_stride 0) or one CalM per scene (27).
+ * Outputs: Rt2, Rt3 (S x 12), T (S x 27), mask (n_total bytes, the flags of scene s at mask[scene_offsets[s] ..]), info (S x 4), status (S).
+ * THE CONTRACT: the outputs of scene s are bit for bit those of tff_robust_pose_dev on that scene alone -- its n_s correspondences, its CalM, the seed
+ * seed + s in wrapping uint64 arithmetic, the same remaining arguments and context options.  Nothing depends on S, on the neighbouring scenes, or on where a
+ * chunk of hypotheses (g = s * n_hyp + h, 262 144 per chunk) ends.
+ * Per-scene failures (the offsets of _dev are device data, so these are statuses, as in the ragged calls): n_s < n_sample gives TFF_ST_TOO_FEW; a decreasing
+ * or negative offset, an offset above n_total or n_s > ns_max gives TFF_ST_BAD_OFFSETS; both with NaN poses, info = [0, -1, 0, 0] and zero flags, the
+ * neighbours unaffected.  No successful hypothesis: TFF_ST_NO_POSE as above.  Whatever the offsets hold, no kernel reads or writes outside [0, n_total) of the
+ * packed arrays; the whole mask is zeroed first.  (Scenes whose ranges overlap -- only malformed offsets make them -- share bytes of the mask: their
+ * results are in bounds and otherwise unspecified.)
+ * TFF_E_INVALID: what tff_robust_pose_dev refuses (the scene size apart), S < 0, S * n_hyp above 2^31 - 1, S * n_cand above the ragged call's 2^28 - 1 items,
+ * a calm_stride other than 0 or 27, n_total or ns_max out of range; _host: decreasing or negative offsets, before any work.  S = 0 returns 0.
+ * _dev: no host synchronisation and no device-to-host copy.  _host: host pointers (n_total and ns_max come from the offsets), one synchronisation.
+ * Workspaces of the context, growing on demand: one chunk of hypotheses (78 doubles each), 4 * S * n_hyp bytes of counts, 49 * n_cand * n_total bytes for the
+ * candidates' flags and packed refits (NOT S * n_cand * ns_max). */
+int tff_robust_pose_scenes_dev(tff_ctx* ctx, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max, int64_t S,
+                               const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
+                               int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status);
+int tff_robust_pose_scenes_host(tff_ctx* ctx, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                                int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
+                                double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status);
+/* Inlier counts of S * per_scene pose hypotheses, hypothesis b against scene b / per_scene with that scene's CalM: counts[b] is what
+ * tff_inlier_count_batch_dev returns for that pose against that scene alone (the same rule per correspondence).  The hypotheses of a scene whose offsets are
+ * negative, decreasing or above n_total count -1.  Four hypotheses per wavefront; a workgroup serves one scene at a time, staged in LDS when it fits 48 KB. */
+int tff_inlier_count_scenes_dev(tff_ctx* ctx, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int64_t S, const double* calm,
+                                int64_t calm_stride, const double* Rt2, const double* Rt3, int64_t per_scene, double threshold, int32_t* counts);
+
 /* ---- multi-GPU (one process, one host thread + stream per device) ----------------------------------
  * The reference runs its triplets one after the other in one MATLAB thread (experiments.m:91-108); they are independent,
  * so a batch is cut into contiguous shards of ceil(B / G) triplets, shard g on device g, with no collective on the data

@@ -117,6 +117,9 @@ def load_library(path=None):
             "tff_inlier_mask_batch_dev": [V, V, I32, V, V, V, I64, F64, V, V],
             "tff_robust_pose_dev": [V, I32, V, I32, V, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
             "tff_robust_pose_host": [V, I32, V, I32, V, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
+            "tff_robust_pose_scenes_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
+            "tff_robust_pose_scenes_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
+            "tff_inlier_count_scenes_dev": [V, V, V, I64, I64, V, I64, V, V, I64, F64, V],
         }
         for name, sig in protos.items():
             fn = getattr(lib, name)
@@ -160,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "tff_multi_create", "tff_multi_destroy", "tff_multi_size", "tff_multi_ctx", "tff_multi_shard", "tff_pose_batch_host_multi", "tff_pose_batch_dev_multi",
     "tff_pose_batch_ragged_dev", "tff_pose_batch_ragged_host",
     "tff_sample_indices_dev", "tff_inlier_mask_batch_dev", "tff_robust_pose_dev", "tff_robust_pose_host",
+    "tff_robust_pose_scenes_dev", "tff_robust_pose_scenes_host", "tff_inlier_count_scenes_dev",
 ]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
@@ -720,6 +724,105 @@ class Context:
             out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
                        status_refined=r["status"][0])
         return out
+
+
+    def _calm_scenes(self, calm, S, dev):
+        """(9, 3) or (S, 9, 3) numpy / torch CalM -> (column-major flat tensor on dev, calm_stride)"""
+        if isinstance(calm, np.ndarray):
+            calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
+        if not isinstance(calm, torch.Tensor) or tuple(calm.shape) not in ((9, 3), (S, 9, 3)):
+            raise ValueError("CalM must be a (9, 3) or (S, 9, 3) array or tensor")
+        if tuple(calm.shape) == (9, 3):
+            calm_cm, stride = calm.t().contiguous().reshape(27), 0
+        else:
+            calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(S * 27), 27
+        return calm_cm.to(device=dev, dtype=torch.float64), stride
+
+    def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None):
+        """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
+        scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
+        with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
+        refits, candidates, status (S,)).  CUDA tensors in (offsets on the device) -> CUDA tensors out, no synchronisation when ns_max, a bound on every
+        scene's size, is passed (it is computed from the offsets with one synchronisation otherwise); a scene with bad offsets or fewer correspondences than a
+        sample gets ST_BAD_OFFSETS / ST_TOO_FEW.  numpy in -> numpy out through the _host form, which refuses malformed offsets."""
+        if method not in ROBUST_METHODS:
+            raise ValueError("robust_pose_scenes draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
+        mid = METHOD_IDS[method]
+        ns = 0 if n_sample is None else int(n_sample)
+        args = (int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_hyp), ns, float(threshold), int(candidates), int(lo_rounds))
+        if isinstance(scenes, np.ndarray):
+            sc = np.ascontiguousarray(scenes, dtype=np.float64)
+            if sc.ndim != 2 or sc.shape[1] != 6:
+                raise ValueError("scenes must be (Ntot, 6)")
+            check_offsets(offsets)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            S = offsets.shape[0] - 1
+            if offsets[-1] > sc.shape[0]:
+                raise ValueError("offsets[-1] = %d beyond the %d packed correspondences" % (offsets[-1], sc.shape[0]))
+            calm_cm, stride = self._calm_cm_np(calm, S)
+            ntot = int(offsets[-1])
+            Rt2 = np.empty((S, 12)); Rt3 = np.empty((S, 12)); T = np.empty((S, 27))
+            mask = np.zeros(sc.shape[0], dtype=np.uint8); info = np.zeros((S, 4), dtype=np.int32); st = np.zeros(S, dtype=np.int32)
+            ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+            _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
+                                                                  ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
+            assert ntot <= mask.shape[0]
+            return dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
+                        T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
+                        candidates=info[:, 3], status=st)
+        if not (isinstance(scenes, torch.Tensor) and scenes.is_cuda and scenes.dtype == torch.float64 and scenes.is_contiguous() and scenes.dim() == 2
+                and scenes.shape[1] == 6):
+            raise ValueError("scenes must be a contiguous float64 CUDA tensor of shape (Ntot, 6)")
+        dev = scenes.device
+        if not (isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.device == dev and offsets.dtype == torch.int64 and offsets.dim() == 1
+                and offsets.shape[0] >= 1):
+            raise ValueError("offsets must be a 1-D int64 tensor of S + 1 entries on the device of scenes")
+        offsets = offsets.contiguous()
+        S = offsets.shape[0] - 1
+        ntot = scenes.shape[0]
+        calm_cm, stride = self._calm_scenes(calm, S, dev)
+        if ns_max is None:                                                   # one synchronisation; pass ns_max to avoid it
+            ns_max = max(0, int((offsets[1:] - offsets[:-1]).max().item())) if S > 0 else 0
+        Rt2 = torch.empty((S, 12), dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
+        T = torch.empty((S, 27), dtype=torch.float64, device=dev)
+        mask = torch.empty(ntot, dtype=torch.uint8, device=dev)
+        info = torch.empty((S, 4), dtype=torch.int32, device=dev); st = torch.empty(S, dtype=torch.int32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
+                                                             stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
+                                                             self._p(st)), "tff_robust_pose_scenes_dev")
+        return dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
+                    mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+
+    def inlier_count_scenes(self, scenes, offsets, calm, R_t_2, R_t_3, threshold=1.0):
+        """Inlier counts of S * per_scene pose hypotheses against S packed scenes (tff_inlier_count_scenes_dev): R_t_2, R_t_3 (S * per_scene, 3, 4),
+        hypothesis b against scene b // per_scene with its CalM ((9, 3) shared or (S, 9, 3)); what inlier_count gives per scene.  -> (S * per_scene,)
+        int32 CUDA tensor, -1 for the hypotheses of a scene with bad offsets.  numpy offsets are validated (check_offsets) before the library is entered."""
+        dev = torch.device("cuda", self.device)
+        if isinstance(offsets, np.ndarray):
+            check_offsets(offsets)
+            offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64))
+        if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.shape[0] < 1 or offsets.dtype != torch.int64:
+            raise ValueError("offsets must be a 1-D int64 array or tensor of S + 1 entries")
+        S = offsets.shape[0] - 1
+        for name, a in (("scenes", scenes), ("R_t_2", R_t_2), ("R_t_3", R_t_3)):
+            want = (6,) if name == "scenes" else (3, 4)
+            if tuple(a.shape[1:]) != want:
+                raise ValueError("%s must be (n, %s)" % (name, ", ".join(map(str, want))))
+        B = R_t_2.shape[0]
+        if R_t_3.shape[0] != B or (S == 0 and B != 0) or (S > 0 and B % S != 0):
+            raise ValueError("R_t_2 and R_t_3 must hold the same multiple of S = %d poses" % S)
+        if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) not in ((9, 3), (S, 9, 3)):
+            raise ValueError("CalM must be a (9, 3) or (S, 9, 3) array or tensor")
+        self._begin()
+        scenes = self._t(scenes); offsets = offsets.to(dev).contiguous()
+        calm_cm, stride = self._calm_scenes(calm, S, dev)
+        r2 = self._cams_cm(self._t(R_t_2)); r3 = self._cams_cm(self._t(R_t_3))
+        cnt = torch.empty(B, dtype=torch.int32, device=dev)
+        _check(self.lib, self.lib.tff_inlier_count_scenes_dev(self.handle, self._p(scenes), self._p(offsets), scenes.shape[0], S, self._p(calm_cm), stride,
+                                                              self._p(r2), self._p(r3), B // S if S else 0, float(threshold), self._p(cnt)),
+               "tff_inlier_count_scenes_dev")
+        return cnt
 
 
 class MultiContext:

@@ -17,6 +17,7 @@
 #include "launch.h"
 #include "ragged_kernel.h"
 #include "robust_kernel.h"
+#include "robust_scenes_kernel.h"
 
 namespace {
 
@@ -126,13 +127,15 @@ constexpr size_t LDS_LIMIT = 160 * 1024;
 // unasked.  (The row kernels, k_tft_moments, k_gh_finish, k_rt_from_tft, k_linear_tft, k_linear_f<., 0> and the staged inlier count ask for an
 // amount that does not grow with N and lies below that, see the static_asserts; for them the check is a no-op.)
 template <class A>
-int launch(tff_ctx* c, void (*kernel)(A), unsigned grid, unsigned block, size_t lds, const A& a) {
+int launch(tff_ctx* c, void (*kernel)(A), dim3 grid, unsigned block, size_t lds, const A& a) {
     if (lds > LDS_LIMIT) return fail(TFF_E_INVALID, "N too large for the 160 KiB LDS workspace of this method");
     if (lds > 64 * 1024) TFF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, c->stream, a);
+    hipLaunchKernelGGL(kernel, grid, dim3(block), lds, c->stream, a);
     TFF_HIP(hipGetLastError());
     return 0;
 }
+template <class A>
+int launch(tff_ctx* c, void (*kernel)(A), unsigned grid, unsigned block, size_t lds, const A& a) { return launch(c, kernel, dim3(grid), block, lds, a); }
 static_assert((((tff::POSE_LDS_DOUBLES + 1) & ~1) + ((tff::JACOBI_LDS_DOUBLES + 1) & ~1)) * sizeof(double) <= 64 * 1024, "pose_lds_bytes(N, 0, .)");
 static_assert((((tff::POSE_LDS_DOUBLES + 1) & ~1) + ((tff::JACOBI_F_LDS_DOUBLES + 1) & ~1)) * sizeof(double) <= 64 * 1024, "f_pose_lds_bytes(N, 0, .)");
 static_assert(tff::ROW_TRIPLETS * sizeof(tff::RowLds) <= 64 * 1024 && 48 * tff::PRE_STAGE_MAX_N + 16 <= 64 * 1024, "rows_lds_bytes, moments_lds_bytes");
@@ -725,7 +728,7 @@ int launch_robust(tff_ctx* c, const RaggedRoute& route, const RobustCall& q) {
     TFF_HIP(hipMemsetAsync(sel, 0, (size_t)K * 8, c->stream));
     const long topk_blocks = (q.n_hyp + tff::ROBUST_TOPK_THREADS - 1) / tff::ROBUST_TOPK_THREADS;
     for (int r = 0; r < K; ++r)
-        TFF_TRY(launch(c, tff::k_robust_topk, (unsigned)(topk_blocks < 1024 ? topk_blocks : 1024), tff::ROBUST_TOPK_THREADS, 0, tff::RobustTopkArgs{counts, (long)q.n_hyp, sel, r}));
+        TFF_TRY(launch(c, tff::k_robust_topk, (unsigned)(topk_blocks < 1024 ? topk_blocks : 1024), tff::ROBUST_TOPK_THREADS, 0, tff::RobustTopkArgs{counts, (long)q.n_hyp, sel, r, K}));
     TFF_TRY(launch_sample_indices(c, q.seed, 0, sel, K, n, Ns, c_idx));
     TFF_TRY(sampled(c_idx, K, s.pose, s.status));
     TFF_TRY(launch(c, tff::k_robust_seed, 1, 64, 0, s));
@@ -746,11 +749,141 @@ int launch_robust(tff_ctx* c, const RaggedRoute& route, const RobustCall& q) {
     return launch_inlier_mask(c, q.scene, Ns, q.calm, q.Rt2, q.Rt3, 1, q.threshold, q.mask, q.info, q.status);
 }
 
+// ---- robust estimation for a batch of scenes (tff_robust_pose_scenes_*, tff_inlier_count_scenes_dev; kernels in robust_scenes_kernel.h) -----------------
+struct ScenesCall {
+    int32_t method; const double* scenes; const int64_t* offsets; int64_t n_total; int32_t ns_max; int64_t S; const double* calm; int64_t calm_stride;
+    uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold; int32_t n_cand; int32_t lo_rounds;
+    double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
+};
+// what can be refused without the offsets: check_robust's list (the scene size apart: too few correspondences is a per-scene status here) and the sizes
+int check_scenes(const tff_ctx* c, ScenesCall* q, const RaggedRoute** route) {
+    RobustCall r{q->method, q->scenes, INT32_MAX, q->calm, q->seed, q->n_hyp, q->n_sample, q->threshold, q->n_cand, q->lo_rounds,
+                 q->Rt2, q->Rt3, q->T, q->mask, q->info, q->status};
+    if (q->S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
+    if (q->n_total < 0 || q->n_total > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_total must be between 0 and 2^31 - 1");
+    if (q->ns_max < 0 || q->ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: ns_max must be between 0 and 2^24");
+    if (q->calm_stride != 0 && q->calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
+    if (!q->offsets) return fail(TFF_E_INVALID, "null offsets");
+    if (q->n_total == 0) { r.scene = q->calm; r.mask = (uint8_t*)q->calm; }  // (nothing packed, no flags: those two pointers may be null)
+    r.Ns = q->n_sample > 0 ? q->n_sample : tff::ROBUST_MAX_SAMPLE;           // (passes check_robust's scene-size tests)
+    TFF_TRY(check_robust(c, &r, route));
+    q->n_sample = r.n_sample;
+    if (q->S > (int64_t)INT32_MAX / q->n_hyp) return fail(TFF_E_INVALID, "robust estimation: S * n_hyp above 2^31 - 1");
+    if (q->S * q->n_cand >= (1L << tff::RETRY_HINT_SHIFT)) return fail(TFF_E_INVALID, "robust estimation: S * n_cand above the ragged call's 2^28 - 1 items");
+    return 0;
+}
+// the inlier counts of B hypotheses, hypothesis b being g = first + b of the call and belonging to scene g / per
+int launch_count_scenes(tff_ctx* c, const tff::SceneSet& set, const double* Rt2, const double* Rt3, int64_t first, int64_t B, int64_t per, double threshold,
+                        int32_t* counts) {
+    const long rows = tff::SCENES_COUNT_ROWS;
+    long grid = (B + rows - 1) / rows;
+    if (grid > 256L * 2) grid = 256L * 2;                                    // two workgroups per CU
+    const long slab = ((B + grid - 1) / grid + rows - 1) / rows * rows;
+    grid = (B + slab - 1) / slab;
+    const long want = 6L * set.ns_max;
+    const int stage = (int)(want < tff::SCENES_STAGE_MAX_DOUBLES ? want : tff::SCENES_STAGE_MAX_DOUBLES);
+    tff::ScenesCountArgs a{set, Rt2, Rt3, (long)first, (long)B, (long)per, slab, threshold, counts, stage};
+    return launch(c, tff::k_inlier_count_scenes, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, ((size_t)36 * rows + (size_t)stage) * sizeof(double), a);
+}
+// device pointers; the lock is held and the context's device current
+int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall& q) {
+    const Method& m = METHODS[q.method];
+    const int K = q.n_cand, n = q.n_sample;
+    const int64_t S = q.S, G = S * q.n_hyp, C = S * K;
+    const tff::SceneSet set{q.scenes, (const long*)q.offsets, (long)S, (long)q.n_total, q.ns_max, n, q.calm, (long)q.calm_stride};
+    if (q.n_total) TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
+    // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate | flags | the packed refit batch
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    const size_t o_sel = carve((size_t)C * 8), o_pose = carve((size_t)C * 51 * 8), o_ref = carve((size_t)C * 51 * 8), o_off = carve((size_t)(C + 1) * 8),
+                 o_int = carve((size_t)C * 7 * 4), o_idx = carve((size_t)C * n * 4), o_calm = carve((size_t)C * 27 * 8),
+                 o_mask = carve((size_t)K * q.n_total), o_pack = carve((size_t)K * q.n_total * 6 * 8);
+    TFF_TRY(c->robust_cand.reserve(off));
+    char* cp = (char*)c->robust_cand.p;
+    unsigned long long* sel = (unsigned long long*)(cp + o_sel);
+    int32_t* ints = (int32_t*)(cp + o_int);
+    tff::ScenesState st{};
+    tff::RobustState& s = st.s;
+    st.q = set; st.K = K; st.cap = (long)K * q.n_total;
+    s.sel = sel; s.K = C; s.Ns = 0;
+    s.cnt = ints; s.seed_idx = ints + C; s.nref = ints + 2 * C; s.status = ints + 3 * C; s.ref_status = ints + 4 * C; s.ref_cnt = ints + 5 * C;
+    int32_t* mask_cnt = ints + 6 * C;
+    s.mask_cnt = mask_cnt;
+    s.pose = (double*)(cp + o_pose); s.ref_pose = (double*)(cp + o_ref);
+    s.offsets = (long*)(cp + o_off);
+    uint8_t* masks = (uint8_t*)(cp + o_mask);
+    s.mask = masks;
+    s.scene = q.scenes; s.packed = (double*)(cp + o_pack);
+    int32_t* c_idx = (int32_t*)(cp + o_idx);
+    double* c_calm = (double*)(cp + o_calm);
+    const tff::ScenesFinishArgs fin{st, q.Rt2, q.Rt3, q.T, q.info, q.status};
+    if (q.n_total == 0)                                                      // no scene can be valid, and the pose kernels must not gather from an empty array
+        return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
+
+    // one chunk of hypotheses: poses (51 doubles) | CalM (27) | status | sample indices
+    const int64_t chunk = G < tff::ROBUST_CHUNK ? G : tff::ROBUST_CHUNK;
+    TFF_TRY(c->robust_hyp.reserve(align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * 27 * sizeof(double)) +
+                                  align256((size_t)chunk * sizeof(int32_t)) + (size_t)chunk * n * sizeof(int32_t)));
+    TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
+    char* hp = (char*)c->robust_hyp.p;
+    double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
+    double* h_calm = (double*)hp;                hp += align256((size_t)chunk * 27 * sizeof(double));
+    int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
+    int32_t* h_idx = (int32_t*)hp;
+    int32_t* counts = (int32_t*)c->robust_counts.p;
+
+    // the method's *_pose_sampled_dev on the packed array: global indices, one CalM per row
+    auto sampled = [&](const int32_t* idx, const double* calm, int64_t B, double* pose, int32_t* status) {
+        PoseCall p{q.scenes, calm, 27, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
+        p.sample_idx = idx; p.sample_ns = (int32_t)q.n_total;
+        return m.launch(c, p);
+    };
+    // 1. hypotheses and their counts, chunk by chunk over g = s * n_hyp + h
+    for (int64_t first = 0; first < G; first += chunk) {
+        const int64_t B = G - first < chunk ? G - first : chunk;
+        TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
+                       tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
+        TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
+        TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, q.n_hyp, q.threshold, counts + first));
+        TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{counts + first, h_status, (long)B}));
+    }
+    // 2. per scene the K best successes, then their poses again from their indices
+    TFF_HIP(hipMemsetAsync(sel, 0, (size_t)C * 8, c->stream));
+    long topk_blocks = (q.n_hyp + tff::ROBUST_TOPK_THREADS - 1) / tff::ROBUST_TOPK_THREADS;
+    if (topk_blocks > 1024) topk_blocks = 1024;
+    for (int64_t s0 = 0; s0 < S; s0 += 65535) {                              // (gridDim.y)
+        const unsigned sy = (unsigned)(S - s0 < 65535 ? S - s0 : 65535);
+        for (int r = 0; r < K; ++r)
+            TFF_TRY(launch(c, tff::k_robust_topk, dim3((unsigned)topk_blocks, sy), tff::ROBUST_TOPK_THREADS, 0,
+                           tff::RobustTopkArgs{counts + s0 * q.n_hyp, (long)q.n_hyp, sel + s0 * K, r, K}));
+    }
+    TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((C + 255) / 256), 256, 0,
+                   tff::ScenesSampleArgs{set, (unsigned long long)q.seed, 0, sel, (long)C, (long)K, n, c_idx, c_calm}));
+    TFF_TRY(sampled(c_idx, c_calm, C, s.pose, s.status));
+    TFF_TRY(launch(c, tff::k_robust_seed, (unsigned)((C + 63) / 64), 64, 0, s));
+    // 3. local optimisation, the candidates of all scenes at once: flags -> packed inliers -> one ragged refit -> counts -> adopt
+    for (int round = 0; round < q.lo_rounds; ++round) {
+        TFF_TRY(launch(c, tff::k_scenes_mask, tff::pose_grid(C), 64, 0,
+                       tff::ScenesMaskArgs{set, s.pose, s.pose + C * 12, (long)C, (long)K, q.threshold, masks, mask_cnt, s.cnt, nullptr}));
+        TFF_TRY(launch(c, tff::k_scenes_offsets, 1, tff::SCENES_SCAN_THREADS, 0, st));
+        TFF_TRY(launch(c, tff::k_scenes_compact, (unsigned)C, tff::ROBUST_COMPACT_THREADS, 0, st));
+        PoseCall p{s.packed, c_calm, 27, C, q.ns_max, s.ref_pose, s.ref_pose + C * 12, s.ref_pose + C * 24, nullptr, nullptr, s.ref_status, nullptr};
+        p.offsets = (const int64_t*)s.offsets;
+        TFF_TRY(launch_ragged(c, route, p));
+        TFF_TRY(launch_count_scenes(c, set, s.ref_pose, s.ref_pose + C * 12, 0, C, K, q.threshold, s.ref_cnt));
+        TFF_TRY(launch(c, tff::k_robust_adopt, (unsigned)C, 64, 0, s));
+    }
+    // 4. per scene the winner, and the flags of its pose in the scene's range of the packed mask (skipped where there is none)
+    TFF_TRY(launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin));
+    return launch(c, tff::k_scenes_mask, tff::pose_grid(S), 64, 0,
+                  tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, nullptr, nullptr, q.status});
+}
+
 }  // namespace
 
 extern "C" {
 
-int tff_version(void) { return 102; }
+int tff_version(void) { return 103; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -981,6 +1114,79 @@ int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_
     TFF_HIP(hipMemcpyAsync(status, d.status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+int tff_robust_pose_scenes_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max, int64_t S,
+                               const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
+                               int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
+    TFF_ENTER(c);
+    ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_scenes(c, &q, &route));
+    if (S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    return launch_robust_scenes(c, *route, q);
+}
+
+// host pointers: the offsets are checked here, n_total and ns_max come from them; H2D, the _dev path, D2H, one synchronisation
+int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                                int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
+                                double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
+    TFF_ENTER(c);
+    if (S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
+    if (!scene_offsets) return fail(TFF_E_INVALID, "null offsets");
+    if (scene_offsets[0] < 0) return fail(TFF_E_INVALID, "robust estimation: negative offset");
+    int64_t ns_max = 0;
+    for (int64_t s = 0; s < S; ++s) {
+        const int64_t ns = scene_offsets[s + 1] - scene_offsets[s];
+        if (ns < 0) return fail(TFF_E_INVALID, "robust estimation: decreasing offsets");
+        if (ns > ns_max) ns_max = ns;
+    }
+    const int64_t n_total = scene_offsets[S];
+    if (ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: a scene of more than 2^24 correspondences");
+    ScenesCall h{method, scenes, scene_offsets, n_total, (int32_t)ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_scenes(c, &h, &route));
+    if (S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    const size_t nscene = (size_t)n_total * 6 * sizeof(double), ncal = (size_t)(calm_stride ? S : 1) * 27 * sizeof(double), nS = (size_t)S;
+    TFF_TRY(c->in.reserve(nscene ? nscene : 8));
+    TFF_TRY(c->calm.reserve(ncal));
+    TFF_TRY(c->ragged_off.reserve((nS + 1) * sizeof(int64_t)));
+    TFF_TRY(c->out.reserve(nS * 51 * sizeof(double) + (size_t)n_total + 8));
+    TFF_TRY(c->idx.reserve(nS * 5 * sizeof(int32_t)));
+    ScenesCall d = h;
+    d.scenes = (const double*)c->in.p; d.calm = (const double*)c->calm.p; d.offsets = (const int64_t*)c->ragged_off.p;
+    d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + nS * 12; d.T = d.Rt3 + nS * 12; d.mask = (uint8_t*)(d.T + nS * 27);
+    d.info = (int32_t*)c->idx.p; d.status = d.info + nS * 4;
+    if (nscene) TFF_HIP(hipMemcpyAsync(c->in.p, scenes, nscene, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(c->ragged_off.p, scene_offsets, (nS + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    TFF_TRY(launch_robust_scenes(c, *route, d));
+    TFF_HIP(hipMemcpyAsync(Rt2, d.Rt2, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(Rt3, d.Rt3, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(T, d.T, nS * 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_total) TFF_HIP(hipMemcpyAsync(mask, d.mask, (size_t)n_total, hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(info, d.info, nS * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(status, d.status, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int tff_inlier_count_scenes_dev(tff_ctx* c, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int64_t S, const double* calm,
+                                int64_t calm_stride, const double* Rt2, const double* Rt3, int64_t per_scene, double threshold, int32_t* counts) {
+    TFF_ENTER(c);
+    if (S < 0 || per_scene < 0) return fail(TFF_E_INVALID, "negative size");
+    if (n_total < 0 || n_total > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "inlier_count_scenes: n_total must be between 0 and 2^31 - 1");
+    if (calm_stride != 0 && calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
+    if (per_scene > 0 && S > (int64_t)INT32_MAX / per_scene) return fail(TFF_E_INVALID, "inlier_count_scenes: S * per_scene above 2^31 - 1");
+    const int64_t B = S * per_scene;
+    return run_batch(c, B, (scenes || n_total == 0) && scene_offsets && calm && Rt2 && Rt3 && counts, "null pointer", nullptr, [&] {
+        const tff::SceneSet set{scenes, (const long*)scene_offsets, (long)S, (long)n_total, INT32_MAX, 0, calm, (long)calm_stride};
+        return launch_count_scenes(c, set, Rt2, Rt3, 0, B, per_scene, threshold, counts);
+    });
 }
 
 

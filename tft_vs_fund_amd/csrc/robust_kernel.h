@@ -45,28 +45,31 @@ struct SampleArgs {
 };
 // One thread per hypothesis: a Fisher-Yates shuffle of the virtual array 0 .. Ns-1 of which only the n swaps are kept (position, value): exactly n
 // draws, no memory proportional to Ns.  Both loops are unrolled over the 16 possible entries so that the list is indexed statically (registers).
-__global__ void __launch_bounds__(256) k_sample_indices(const SampleArgs a) {
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
-    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(a.first + b);
-    const unsigned long long key = splitmix64(a.seed ^ (h * 0xD1342543DE82EF95ULL));
+// sample_draw: the n indices of hypothesis h under `seed`, each plus `base` (the scene's first correspondence in a packed array, robust_scenes_kernel.h)
+__device__ __forceinline__ void sample_draw(const unsigned long long seed, const unsigned long long h, const int n, const int Ns, const int base, int* out) {
+    const unsigned long long key = splitmix64(seed ^ (h * 0xD1342543DE82EF95ULL));
     int pos[ROBUST_MAX_SAMPLE], val[ROBUST_MAX_SAMPLE];
-    int* out = a.out + b * a.n;
 #pragma unroll
     for (int i = 0; i < ROBUST_MAX_SAMPLE; ++i) {
-        if (i < a.n) {
+        if (i < n) {
             const unsigned long long u = splitmix64(key + (unsigned long long)i) >> 32;
-            const int r = i + (int)((u * (unsigned long long)(a.Ns - i)) >> 32);
+            const int r = i + (int)((u * (unsigned long long)(Ns - i)) >> 32);
             int vr = r, vi = i;              // the value at a position: that of the LAST swap recorded there, else the position itself
 #pragma unroll
             for (int j = 0; j < i; ++j) {
                 vr = (pos[j] == r) ? val[j] : vr;
                 vi = (pos[j] == i) ? val[j] : vi;
             }
-            out[i] = vr;
+            out[i] = base + vr;
             pos[i] = r; val[i] = vi;
         }
     }
+}
+__global__ void __launch_bounds__(256) k_sample_indices(const SampleArgs a) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(a.first + b);
+    sample_draw(a.seed, h, a.n, a.Ns, 0, a.out + b * a.n);
 }
 
 // ---- per-correspondence inlier flags ------------------------------------------------------------------------------------------------------------
@@ -128,20 +131,24 @@ __global__ void __launch_bounds__(256) k_robust_mark(const RobustMarkArgs a) {
 
 // The order of the candidates is (count descending, hypothesis index ascending) = descending key (count + 1) << 32 | (2^32 - 1 - index); keys are
 // distinct, so round r takes the largest key below the one round r - 1 took and nothing has to be marked.  A key of 0 = nothing left.
+// blockIdx.y is the scene (one for tff_robust_pose_*): its counts at counts + y * n_hyp, its keys at sel + y * K, the keys built from h within the scene.
 struct RobustTopkArgs {
-    const int* counts;       // n_hyp, -1 = failed
+    const int* counts;       // n_hyp per scene, -1 = failed
     long n_hyp;
-    unsigned long long* sel; // K keys, zero on entry
+    unsigned long long* sel; // K keys per scene, zero on entry
     int round;
+    int K;
 };
 constexpr int ROBUST_TOPK_THREADS = 256;
 __global__ void __launch_bounds__(ROBUST_TOPK_THREADS) k_robust_topk(const RobustTopkArgs a) {
     __shared__ unsigned long long part[ROBUST_TOPK_THREADS / 64];
-    const unsigned long long below = a.round ? a.sel[a.round - 1] : ~0ULL;
+    const int* counts = a.counts + (long)blockIdx.y * a.n_hyp;
+    unsigned long long* sel = a.sel + (long)blockIdx.y * a.K;
+    const unsigned long long below = a.round ? sel[a.round - 1] : ~0ULL;
     unsigned long long best = 0;
     if (below != 0) {
         for (long h = (long)blockIdx.x * blockDim.x + threadIdx.x; h < a.n_hyp; h += (long)gridDim.x * blockDim.x) {
-            const int c = a.counts[h];
+            const int c = counts[h];
             const unsigned long long key = ((unsigned long long)(c + 1) << 32) | (0xFFFFFFFFULL - (unsigned long long)h);
             if (c >= 0 && key < below && key > best) best = key;
         }
@@ -156,14 +163,14 @@ __global__ void __launch_bounds__(ROBUST_TOPK_THREADS) k_robust_topk(const Robus
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int w = 1; w < ROBUST_TOPK_THREADS / 64; ++w) best = part[w] > best ? part[w] : best;
-        if (best) atomicMax(a.sel + a.round, best);
+        if (best) atomicMax(sel + a.round, best);
     }
 }
 
 // The state of the K candidates, all device-resident
 struct RobustState {
     const unsigned long long* sel;   // K selection keys
-    int K;
+    long K;
     int Ns;
     int* cnt;                // K current inlier counts, -1 = no such candidate
     int* seed_idx;           // K hypothesis indices
@@ -182,7 +189,7 @@ struct RobustState {
 // runs after the candidates' hypotheses were recomputed from their keys (k_sample_indices with `keys`, the *_sampled pose kernels).  A candidate
 // whose recomputed hypothesis is not a success cannot exist -- it was selected among the successes -- the test of its status is a guard
 __global__ void __launch_bounds__(64) k_robust_seed(const RobustState s) {
-    const int r = (int)threadIdx.x;
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;              // (one workgroup for K <= 64; S * K candidates: robust_scenes_kernel.h)
     if (r >= s.K) return;
     const unsigned long long key = s.sel[r];
     const bool valid = key != 0 && s.status[r] == 0;
@@ -231,9 +238,10 @@ __global__ void __launch_bounds__(ROBUST_COMPACT_THREADS) k_robust_compact(const
     }
 }
 __global__ void __launch_bounds__(64) k_robust_adopt(const RobustState s) {
-    const int r = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const long r = (long)blockIdx.x;                                        // (long: S * K candidates index these arrays too, robust_scenes_kernel.h)
+    const int lane = (int)threadIdx.x;
     if (s.cnt[r] < 0 || s.ref_status[r] != 0 || s.ref_cnt[r] < s.cnt[r]) return;
-    const int K = s.K;
+    const long K = s.K;
     if (lane < 12) { s.pose[r * 12 + lane] = s.ref_pose[r * 12 + lane]; s.pose[(K + r) * 12 + lane] = s.ref_pose[(K + r) * 12 + lane]; }
     if (lane < 27) s.pose[K * 24 + r * 27 + lane] = s.ref_pose[K * 24 + r * 27 + lane];
     __syncthreads();                                                         // (the count is read above by every lane before lane 0 replaces it)
@@ -246,7 +254,7 @@ struct RobustFinishArgs {
     int* status;             // 1
 };
 __global__ void __launch_bounds__(64) k_robust_finish(const RobustFinishArgs a) {
-    const int lane = (int)threadIdx.x, K = a.s.K;
+    const int lane = (int)threadIdx.x, K = (int)a.s.K;
     int win = -1, best = -1, ncand = 0;
     for (int r = 0; r < K; ++r) {
         const int c = a.s.cnt[r];
