@@ -61,6 +61,7 @@ typedef struct tff_ctx tff_ctx;
 #define TFF_ST_NO_PARAM 5   /* PiColPoseEstimation.m:84-89: error('The minimal param could not be found') */
 #define TFF_ST_RANK 4       /* Nordberg: P2(:,1:3) or P3(:,1:3) of rank < 2 (NordbergTFT...m:58,60 would fail: null() returns two columns) */
 #define TFF_ST_BAD_OFFSETS 6 /* ragged calls (_dev): offsets[b+1] < offsets[b], offsets[b] < 0, or n_b > n_max -- NaN poses for that item only */
+#define TFF_ST_TOO_LARGE 7   /* ragged BA: more selected correspondences than TFF_BA_MAX_N */
 
 /* error codes (besides -hipError_t) */
 #define TFF_E_INVALID (-10001)
@@ -99,6 +100,9 @@ typedef struct tff_ctx tff_ctx;
                              * (profiles/r5_ab_pre.txt) -- the path is bound by fp64 issue, not by those passes' memory waits.  Results agree to rounding */
 #define TFF_OPT_COUNT_ROWS 11 /* tff_inlier_count_batch_dev on many hypotheses of one scene: 1 (default) four hypotheses per wavefront, one per row of 16 lanes
                              * (the cameras composed once per row, 25 trips of 16 over a 400-correspondence scene); 0 one hypothesis per wavefront.  Identical counts */
+#define TFF_OPT_BA_CLASSES 12 /* tff_bundle_adjust_ragged_*: how the items are launched.  0 (default): by batch size -- up to 256 items (every item resident at once
+                             * even at one wavefront per CU) one launch sized for TFF_BA_MAX_N, larger batches three launch classes by LDS need; 1 = one
+                             * launch always; 2 = three classes always (A/B switch, tools/bench_ba_ragged.py).  Identical results */
 #define TFF_OPT_DEBUG_FP_HANDOVER 8 /* test hook: 1 = FaugPapa's block kernel hands every third triplet back to the generic workgroup kernel, as it does when its
                              * pseudo-inverse reports a failure (exercises that production fall-back; results must not depend on it beyond the
                              * generic kernel's LAPACK-level noise) */
@@ -272,6 +276,42 @@ int tff_bundle_adjust_batch_dev(tff_ctx* ctx, const double* calm, int64_t calm_s
 int tff_bundle_adjust_batch_host(tff_ctx* ctx, const double* calm, int64_t calm_stride, const double* Rt2_in,
                                  const double* Rt3_in, const double* corresp, int64_t B, int32_t N, const double* reconst0,
                                  double* Rt2, double* Rt3, double* reconst, int32_t* iter, double* repr_err, int32_t* status);
+
+/* ---- ragged, masked BundleAdjustment: one call for items with different correspondence counts, e.g. the polish of tff_robust_pose_scenes_* ------------
+ * corresp, offsets: packed as in tff_pose_batch_ragged_* (item b owns the n_b correspondences offsets[b] .. offsets[b+1]-1; offsets on the device for
+ * _dev).  n_total (host, in [0, 2^31 - 1]) bounds every offset and sizes the workspaces.  mask: NULL, or n_total bytes, the byte of correspondence n of
+ * item b at offsets[b] + n, non-zero = use it -- exactly the `mask` tff_robust_pose_scenes_* writes.  m_b = the number of selected correspondences of
+ * item b (n_b without a mask).  calm, Rt2_in, Rt3_in, Rt2, Rt3, iter, repr_err, status: per item, as tff_bundle_adjust_batch_dev.  reconst0, reconst
+ * (each may be NULL): 3 doubles per packed correspondence at (offsets[b] + n) * 3; reconst0 is read at selected positions only, reconst gets NaN at the
+ * unselected positions of a valid item.  used (B int32, may be NULL) receives m_b.
+ * THE CONTRACT: the outputs of item b -- Rt2, Rt3, reconst at the selected positions, iter, repr_err, status -- are bit for bit those of
+ * tff_bundle_adjust_batch_dev called with B = 1, N = m_b, the item's selected correspondences in packed order, its poses, its CalM, its selected reconst0
+ * triples and the same context options: one kernel serves both calls, with the same instruction stream per item.  Nothing depends on B, on the
+ * neighbouring items or on the order in which the launch plan lists the items.
+ * Per-item failures (statuses, the offsets of _dev being device data); the item gets NaN poses and repr_err, iter 0 and used 0, its neighbours are
+ * unaffected: a negative or decreasing offset or one above n_total gives TFF_ST_BAD_OFFSETS and leaves the item's reconst range untouched; m_b = 0 gives
+ * TFF_ST_TOO_FEW; m_b > TFF_BA_MAX_N gives TFF_ST_TOO_LARGE (the points of an item live in LDS); the last two write NaN over the item's reconst range.
+ * Whatever the offsets hold, no kernel reads or writes outside [0, n_total) of the packed arrays.  (Items whose ranges overlap -- only malformed offsets
+ * make them -- share positions of reconst: their points are in bounds and otherwise unspecified; with a mask, an item whose selection would not fit the
+ * n_total slots of the compact workspace after the items before it is TFF_ST_BAD_OFFSETS.)
+ * The launch plan: the kernel needs 13 872 + 48 m bytes of LDS and runs four wavefronts per CU while an item needs at most 40 KiB, two up to 80 KiB, one
+ * up to 160 KiB.  The items are sorted on the device into three classes by m_b (tff_bundle_adjust_ragged_class_bounds: the largest m of each class,
+ * bounds[2] = TFF_BA_MAX_N) and every class gets its own launch with its own LDS size, so a few large items do not cost the small ones their occupancy.
+ * The class launches follow one another on the stream, so a batch of at most 256 items, all resident at once anyway, takes ONE launch sized for
+ * TFF_BA_MAX_N instead (TFF_OPT_BA_CLASSES; B is a host value).  The results do not depend on the plan.
+ * TFF_E_INVALID: a null required pointer, B < 0, n_total outside [0, 2^31 - 1], a calm_stride other than 0 or 27; _host only: decreasing or negative
+ * offsets, before any work.  B = 0 returns 0.
+ * _dev: no host synchronisation and no device-to-host copy.  _host: host pointers (n_total is offsets[B]), one synchronisation.
+ * Workspaces of the context, growing on demand: 24 B bytes for the plan; with a mask, 100 bytes x n_total for the compact copies (correspondences,
+ * reconst0, points, source indices); status == NULL borrows the status scratch. */
+#define TFF_BA_MAX_N 3124    /* largest N whose 13 872 + 48 N bytes of LDS fit the 160 KiB limit (checked against the kernel's ba_lds_bytes at compile time) */
+int tff_bundle_adjust_ragged_dev(tff_ctx* ctx, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
+                                 int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2,
+                                 double* Rt3, double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status);
+int tff_bundle_adjust_ragged_host(tff_ctx* ctx, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm,
+                                  int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2,
+                                  double* Rt3, double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status);
+int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]);
 
 /* BundleAdjustment (Optimization/BundleAdjustment.m:49-216) as the reference writes it, for M = 2 .. 6 views, in MATLAB's own
  * array layouts so that a gateway passes its arguments through: calm = CalM (3M x 3, column-major; calm_stride 0 = shared, 9M =

@@ -40,10 +40,13 @@ TFF_OPT_DEBUG_FP_HANDOVER = 8
 TFF_OPT_DEBUG_ADAPTIVE = 9
 TFF_OPT_PRE = 10
 TFF_OPT_COUNT_ROWS = 11
+TFF_OPT_BA_CLASSES = 12
 DEBUG_STRIDE = 128
 
 ST_OK, ST_TOO_FEW, ST_NONFINITE, ST_NO_POSE, ST_RANK, ST_NO_PARAM = 0, 1, 2, 3, 4, 5
 ST_BAD_OFFSETS = 6
+ST_TOO_LARGE = 7             # ragged bundle adjustment: more selected correspondences than BA_MAX_N
+BA_MAX_N = 3124              # include/tftfund.h TFF_BA_MAX_N
 ROBUST_CHUNK = 262144        # hypotheses per chunk of tff_robust_pose_* (csrc/robust_kernel.h); the result does not depend on it
 
 _c_dp = ctypes.c_void_p
@@ -120,6 +123,9 @@ def load_library(path=None):
             "tff_robust_pose_scenes_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
             "tff_robust_pose_scenes_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
             "tff_inlier_count_scenes_dev": [V, V, V, I64, I64, V, I64, V, V, I64, F64, V],
+            "tff_bundle_adjust_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
+            "tff_bundle_adjust_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
+            "tff_bundle_adjust_ragged_class_bounds": [V],
         }
         for name, sig in protos.items():
             fn = getattr(lib, name)
@@ -164,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "tff_pose_batch_ragged_dev", "tff_pose_batch_ragged_host",
     "tff_sample_indices_dev", "tff_inlier_mask_batch_dev", "tff_robust_pose_dev", "tff_robust_pose_host",
     "tff_robust_pose_scenes_dev", "tff_robust_pose_scenes_host", "tff_inlier_count_scenes_dev",
+    "tff_bundle_adjust_ragged_dev", "tff_bundle_adjust_ragged_host", "tff_bundle_adjust_ragged_class_bounds",
 ]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
@@ -245,6 +252,15 @@ def check_offsets(offsets):
     return int(n.max()) if n.size else 0
 
 
+def ba_ragged_class_bounds():
+    """tff_bundle_adjust_ragged_class_bounds: the largest number of selected correspondences of each of the three launch classes of
+    Context.bundle_adjust_ragged (LDS per item up to 40, 80, 160 KiB); the last one is BA_MAX_N."""
+    lib = load_library()
+    b = (ctypes.c_int32 * 3)()
+    _check(lib, lib.tff_bundle_adjust_ragged_class_bounds(b), "tff_bundle_adjust_ragged_class_bounds")
+    return tuple(int(v) for v in b)
+
+
 def _check(lib, rc, what):
     if rc != 0:
         msg = lib.tff_last_error()
@@ -282,6 +298,11 @@ class Context:
     def set_count_rows(self, on):
         """TFF_OPT_COUNT_ROWS: inlier counts with four hypotheses per wavefront (default) or one."""
         _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_COUNT_ROWS, int(bool(on))), "set_option")
+
+    def set_ba_classes(self, mode):
+        """TFF_OPT_BA_CLASSES: how bundle_adjust_ragged launches its items.  "auto" / 0 (default) = one launch sized for BA_MAX_N up to 256 items, three
+        launch classes by LDS need beyond; 1 = one launch always; 2 = three classes always (A/B switch).  Identical results."""
+        _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_BA_CLASSES, 0 if mode == "auto" else int(mode)), "set_option")
 
     def set_rows(self, on):
         """TFF_OPT_ROWS: "auto" / 2 (default) and True / 1 = the row kernels (four triplets per wavefront, one per row of 16 lanes) at any batch size:
@@ -606,6 +627,86 @@ class Context:
         return dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec.transpose(1, 2),
                     iter=it, repr_err=err, status=st)
 
+    def bundle_adjust_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, mask=None, reconst0=None, reconst=True):
+        """BundleAdjustment for B items with different correspondence counts in one call (tff_bundle_adjust_ragged_*): corresp (Ntot, 6) packed,
+        offsets (B + 1,) int64 with item b = corresp[offsets[b]:offsets[b + 1]] (see pack_ragged), mask None or (Ntot,) uint8 / bool (non-zero = use the
+        correspondence: the `mask` of robust_pose_scenes), calm (9, 3) or (B, 9, 3), R_t_2, R_t_3 (B, 3, 4), reconst0 None or (Ntot, 3) (read where
+        selected).  Item b gets bit for bit what bundle_adjust returns for its selected correspondences alone.  CUDA tensors in (offsets on the device)
+        -> CUDA tensors out, no synchronisation; numpy in -> numpy out through the _host form (malformed offsets raise).
+        Returns dict(R_t_2, R_t_3 (B,3,4), Reconst (Ntot,3) or None -- NaN where not selected --, iter, repr_err, used, status (B,)); per item
+        ST_BAD_OFFSETS / ST_TOO_FEW (nothing selected) / ST_TOO_LARGE (more than BA_MAX_N selected) with NaN poses."""
+        host = isinstance(corresp, np.ndarray)
+        if host:
+            offsets = np.asarray(offsets)
+            check_offsets(offsets)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            corresp = np.ascontiguousarray(corresp, dtype=np.float64)
+            if corresp.ndim != 2 or corresp.shape[1] != 6:
+                raise ValueError("corresp must be (Ntot, 6)")
+            if offsets[-1] > corresp.shape[0]:
+                raise ValueError("offsets[-1] = %d beyond the %d packed correspondences" % (offsets[-1], corresp.shape[0]))
+        else:
+            if not (isinstance(corresp, torch.Tensor) and corresp.is_cuda and corresp.dtype == torch.float64 and corresp.is_contiguous() and corresp.dim() == 2
+                    and corresp.shape[1] == 6):
+                raise ValueError("corresp must be a contiguous float64 CUDA tensor of shape (Ntot, 6)")
+            if not (isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.device == corresp.device and offsets.dtype == torch.int64
+                    and offsets.dim() == 1 and offsets.shape[0] >= 1):
+                raise ValueError("offsets must be a 1-D int64 tensor of B + 1 entries on the device of corresp")
+            offsets = offsets.contiguous()
+        B = offsets.shape[0] - 1
+        ntot = corresp.shape[0]
+        for name, a in (("R_t_2", R_t_2), ("R_t_3", R_t_3)):
+            if tuple(a.shape) != (B, 3, 4):
+                raise ValueError("%s must be (B, 3, 4) with B = %d" % (name, B))
+        if mask is not None and tuple(mask.shape) != (ntot,):
+            raise ValueError("mask must hold one flag per packed correspondence: (%d,)" % ntot)
+        if reconst0 is not None and tuple(reconst0.shape) != (ntot, 3):
+            raise ValueError("reconst0 must be (Ntot, 3), packed like corresp")
+        if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) not in ((9, 3), (B, 9, 3)):
+            raise ValueError("CalM must be a (9, 3) or (B, 9, 3) array or tensor")
+        if host:
+            to_np = lambda a, dt=np.float64: np.ascontiguousarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)
+            calm_cm, stride = self._calm_cm_np(to_np(calm), B)
+            r2 = np.ascontiguousarray(to_np(R_t_2).transpose(0, 2, 1)); r3 = np.ascontiguousarray(to_np(R_t_3).transpose(0, 2, 1))
+            mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            x0 = None if reconst0 is None else to_np(reconst0)
+            o2 = np.empty((B, 12)); o3 = np.empty((B, 12))
+            rec = np.full((ntot, 3), np.nan) if reconst else None
+            it = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32); used = np.zeros(B, dtype=np.int32); err = np.empty(B)
+            ptr = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None else None
+            _check(self.lib, self.lib.tff_bundle_adjust_ragged_host(self.handle, ptr(corresp), ptr(offsets), ptr(mk), ptr(calm_cm), stride, ptr(r2), ptr(r3),
+                                                                    ptr(x0), B, ptr(o2), ptr(o3), ptr(rec), ptr(it), ptr(err), ptr(used), ptr(st)),
+                   "tff_bundle_adjust_ragged_host")
+            return dict(R_t_2=o2.reshape(B, 4, 3).transpose(0, 2, 1), R_t_3=o3.reshape(B, 4, 3).transpose(0, 2, 1), Reconst=rec, iter=it, repr_err=err,
+                        used=used, status=st)
+        dev = corresp.device
+        calm_cm, stride = self._calm_scenes(calm, B, dev)
+        on_dev = lambda a, dt: (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(device=dev, dtype=dt)
+        r2 = on_dev(R_t_2, torch.float64).transpose(1, 2).contiguous(); r3 = on_dev(R_t_3, torch.float64).transpose(1, 2).contiguous()
+        mk = None if mask is None else on_dev(mask, torch.uint8).contiguous()       # (bool -> 0 / 1)
+        x0 = None if reconst0 is None else on_dev(reconst0, torch.float64).contiguous()
+        o2 = torch.empty((B, 12), dtype=torch.float64, device=dev); o3 = torch.empty_like(o2)
+        rec = torch.full((ntot, 3), float("nan"), dtype=torch.float64, device=dev) if reconst else None
+        it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it); used = torch.zeros_like(it)
+        err = torch.empty(B, dtype=torch.float64, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        _check(self.lib, self.lib.tff_bundle_adjust_ragged_dev(self.handle, self._p(corresp), self._p(offsets), ntot, self._p(mk), self._p(calm_cm), stride,
+                                                               self._p(r2), self._p(r3), self._p(x0), B, self._p(o2), self._p(o3), self._p(rec), self._p(it),
+                                                               self._p(err), self._p(used), self._p(st)), "tff_bundle_adjust_ragged_dev")
+        return dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec, iter=it, repr_err=err, used=used,
+                    status=st)
+
+    def _polish(self, out, calm, scenes, offsets, single):
+        """the polish of robust_pose / robust_pose_scenes: ONE bundle_adjust_ragged call on the result's poses and mask"""
+        r2, r3 = out["R_t_2"], out["R_t_3"]
+        if single:
+            r2, r3 = r2[None], r3[None]
+        ba = self.bundle_adjust_ragged(calm, r2, r3, scenes, offsets, mask=out["mask"], reconst=False)
+        pick = (lambda a: a[0]) if single else (lambda a: a)
+        out.update(R_t_2_polished=pick(ba["R_t_2"]), R_t_3_polished=pick(ba["R_t_3"]), iter_polished=pick(ba["iter"]),
+                   repr_err_polished=pick(ba["repr_err"]), status_polished=pick(ba["status"]))
+        return out
+
     def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None):
         """BundleAdjustment for B problems of M = 2 .. 6 views (tff_bundle_adjust_views_batch_dev): calm (3M,3) or (B,3M,3); R_t_0 (B,3M,4),
         first camera included and free; corresp (B,N,2M), NaN = not seen (drops the whole view, as the reference's code does); reconst0 (B,3,N) or
@@ -670,13 +771,14 @@ class Context:
                                                             float(threshold), self._p(mask), self._p(cnt)), "tff_inlier_mask_batch_dev")
         return (mask, cnt) if with_counts else mask
 
-    def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None):
+    def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False):
         """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
         best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
         Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
         -> CUDA tensors (0-d for the five scalars) and no synchronisation; numpy in -> numpy / ints (the _host form).  refine = a name in POSE_METHODS:
         that method once on the final inliers through pose_batch (reads the count on the host), as R_t_2_refined, R_t_3_refined, T_refined,
-        iter_refined, status_refined."""
+        iter_refined, status_refined.  polish=True: BundleAdjustment on the pose and its inliers in one more call (bundle_adjust_ragged with the mask and the
+        offsets [0, Ns], built on the device; no synchronisation and no copy on the device path), as R_t_2_polished, R_t_3_polished, iter_polished, repr_err_polished, status_polished."""
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
@@ -723,6 +825,13 @@ class Context:
             r = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
             out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
                        status_refined=r["status"][0])
+        if polish:
+            if isinstance(scene, np.ndarray):
+                self._polish(out, calm, sc, np.array([0, Ns], dtype=np.int64), True)
+                out["iter_polished"] = int(out["iter_polished"]); out["status_polished"] = int(out["status_polished"])
+                out["repr_err_polished"] = float(out["repr_err_polished"])
+            else:
+                self._polish(out, calm, scene, torch.arange(2, dtype=torch.int64, device=dev) * Ns, True)   # [0, Ns], made on the device
         return out
 
 
@@ -738,13 +847,16 @@ class Context:
             calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(S * 27), 27
         return calm_cm.to(device=dev, dtype=torch.float64), stride
 
-    def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None):
+    def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
+                           polish=False):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
         refits, candidates, status (S,)).  CUDA tensors in (offsets on the device) -> CUDA tensors out, no synchronisation when ns_max, a bound on every
         scene's size, is passed (it is computed from the offsets with one synchronisation otherwise); a scene with bad offsets or fewer correspondences than a
-        sample gets ST_BAD_OFFSETS / ST_TOO_FEW.  numpy in -> numpy out through the _host form, which refuses malformed offsets."""
+        sample gets ST_BAD_OFFSETS / ST_TOO_FEW.  numpy in -> numpy out through the _host form, which refuses malformed offsets.
+        polish=True: BundleAdjustment on every scene's pose and inliers in ONE more call (bundle_adjust_ragged on the result's poses and mask), as
+        R_t_2_polished, R_t_3_polished (S,3,4), iter_polished, repr_err_polished, status_polished (S,); a scene without a pose gets ST_TOO_FEW there."""
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose_scenes draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         mid = METHOD_IDS[method]
@@ -767,9 +879,10 @@ class Context:
             _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
                                                                   ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
             assert ntot <= mask.shape[0]
-            return dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
-                        T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
-                        candidates=info[:, 3], status=st)
+            out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
+                       T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
+                       candidates=info[:, 3], status=st)
+            return self._polish(out, calm, sc, offsets, False) if polish else out
         if not (isinstance(scenes, torch.Tensor) and scenes.is_cuda and scenes.dtype == torch.float64 and scenes.is_contiguous() and scenes.dim() == 2
                 and scenes.shape[1] == 6):
             raise ValueError("scenes must be a contiguous float64 CUDA tensor of shape (Ntot, 6)")
@@ -791,8 +904,9 @@ class Context:
         _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
                                                              stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
                                                              self._p(st)), "tff_robust_pose_scenes_dev")
-        return dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
-                    mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
+                   mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        return self._polish(out, calm, scenes, offsets, False) if polish else out
 
     def inlier_count_scenes(self, scenes, offsets, calm, R_t_2, R_t_3, threshold=1.0):
         """Inlier counts of S * per_scene pose hypotheses against S packed scenes (tff_inlier_count_scenes_dev): R_t_2, R_t_3 (S * per_scene, 3, 4),

@@ -43,6 +43,11 @@ struct BaArgs {
     const double* reconst0;                          // B x 3N or null: triangulate first (:59-77)
     double* Rt2; double* Rt3; double* reconst;       // outputs (reconst may be null)
     int* iter; double* repr_err; int* status;
+    // Ragged batches (ba_ragged_kernel.h), all null for the fixed-N call.  The block's index is then a SLOT of `items`, a list of item indices that
+    // ends at the device-side *count (B is only its capacity); item b has item_n[b] correspondences, the first one at index item_off[b] of corresp,
+    // reconst0 and reconst.  Everything else -- the poses, CalM, iter, repr_err, status -- is indexed by the item, and the body below is the same
+    // instruction stream for both forms: same item, same N, same bits.
+    const int* items = nullptr; const int* count = nullptr; const int* item_n = nullptr; const long* item_off = nullptr;
 };
 
 // lane 0: rotation products of one camera from its three angles
@@ -204,10 +209,20 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
     BaLds* L = reinterpret_cast<BaLds*>(smem + base);
     double* Xc = smem + base + ((BA_LDS_DOUBLES + 1) & ~1);                  // current points (3N), then trial points (3N)
     const int lane = lane_id();
-    for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const int N = opaque_int(a.N);                                       // (not hoisted out of the one-trip triplet loop: tft_kernel.h)
+    for (long slot = blockIdx.x; slot < a.B; slot += gridDim.x) {
+        long b = slot, first;                                                // the item, and the index of its first correspondence
+        int N;
+        if (a.items) {
+            if (slot >= (long)*a.count) break;                               // (before anything is touched: the class has fewer items than the launch has blocks)
+            b = wave_uniform_i(a.items[slot]);
+            N = opaque_int(wave_uniform_i(a.item_n[b]));
+            first = a.item_off[b];
+        } else {
+            N = opaque_int(a.N);                                             // (not hoisted out of the one-trip triplet loop: tft_kernel.h)
+            first = b * (long)N;
+        }
         double* Xt = Xc + 3 * N;
-        const double* pts = a.corresp + b * 6 * (long)N;
+        const double* pts = a.corresp + 6 * first;
         wave_sync();
         if (lane < 27) w->calm[lane] = a.calm[b * a.calm_stride + lane];
         wave_sync();
@@ -228,7 +243,7 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
         }
         wave_sync();
         if (a.reconst0) {
-            for (int e = lane; e < 3 * N; e += WAVE) Xc[e] = a.reconst0[b * 3 * (long)N + e];
+            for (int e = lane; e < 3 * N; e += WAVE) Xc[e] = a.reconst0[3 * first + e];
         } else {                                                             // initial triangulation with the given poses   (:59-77)
             if (lane < 12) {
                 const int r = lane >> 2, c = lane & 3;
@@ -330,7 +345,7 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
             double* out = (lane == 0 ? a.Rt2 : a.Rt3) + b * 12;
             for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) out[r + 3 * c] = R.m[r][c]; out[9 + r] = scale * L->cur.c[6 + 3 * lane + r]; }
         }
-        if (a.reconst) for (int e = lane; e < 3 * N; e += WAVE) a.reconst[b * 3 * (long)N + e] = scale * Xc[e];
+        if (a.reconst) for (int e = lane; e < 3 * N; e += WAVE) a.reconst[3 * first + e] = scale * Xc[e];
         const bool bad = !(fabs(S) <= 1.79e308);
         if (bad && status == ST_OK) status = ST_NONFINITE;
         if (lane == 0) {
@@ -341,7 +356,7 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
     }
 }
 
-inline size_t ba_lds_bytes(int N) {
+constexpr size_t ba_lds_bytes(int N) {
     return (size_t)(((POSE_LDS_DOUBLES + 1) & ~1) + ((BA_LDS_DOUBLES + 1) & ~1) + 6 * (size_t)N) * sizeof(double);
 }
 

@@ -18,6 +18,7 @@
 #include "ragged_kernel.h"
 #include "robust_kernel.h"
 #include "robust_scenes_kernel.h"
+#include "ba_ragged_kernel.h"
 
 namespace {
 
@@ -74,6 +75,7 @@ struct tff_ctx {
     DevBuf in, calm, out, idx, scratch_status, gh_rec, gh_topt, gh_init, spill, pre_rec, retry;
     DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
     DevBuf robust_hyp, robust_counts, robust_cand;   // tff_robust_pose_*: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust)
+    DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
     int spill_only_if_needed = 0;          // TFF_OPT_SPILL
@@ -83,6 +85,7 @@ struct tff_ctx {
     int dbg_fp_handover = 0;               // TFF_OPT_DEBUG_FP_HANDOVER
     int dbg_adaptive = 0;                  // TFF_OPT_DEBUG_ADAPTIVE
     int count_rows = 1;                    // TFF_OPT_COUNT_ROWS: inlier counts four hypotheses per wavefront (default) or one
+    int ba_classes = 0;                    // TFF_OPT_BA_CLASSES: ragged bundle adjustment, 0 the plan by batch size (launch_ba_ragged), 1 one launch class, 2 three
 };
 
 namespace {
@@ -909,7 +912,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand})
+                      &c->robust_cand, &c->ba_plan, &c->ba_pack, &c->ba_host})
         b->release();
     delete c;
 }
@@ -959,6 +962,7 @@ int tff_ctx_set_option(tff_ctx* c, int option, long value) {
         case TFF_OPT_ROWS: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "rows must be 0, 1 or 2"); c->rows = (int)value; return 0;
         case TFF_OPT_PRE: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "pre must be 0, 1 or 2"); c->pre = (int)value; return 0;
         case TFF_OPT_COUNT_ROWS: c->count_rows = value != 0; return 0;
+        case TFF_OPT_BA_CLASSES: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "ba_classes must be 0, 1 or 2"); c->ba_classes = (int)value; return 0;
         case TFF_OPT_DEBUG_FP_HANDOVER: c->dbg_fp_handover = value != 0; return 0;
         case TFF_OPT_DEBUG_ADAPTIVE: c->dbg_adaptive = value != 0; return 0;
         case TFF_OPT_KERNEL: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "kernel must be 0, 1 or 2"); c->kernel_variant = (int)value; return 0;
@@ -1264,6 +1268,72 @@ int launch_bundle_adjust(tff_ctx* c, const tff::BaArgs& a) {
     if (a.N < 1) return fail(TFF_E_INVALID, "bundle adjustment needs at least one correspondence");
     return launch(c, tff::k_bundle_adjust, tff::pose_grid(a.B), 64, tff::ba_lds_bytes(a.N), a);
 }
+// ---- ragged, masked bundle adjustment (tff_bundle_adjust_ragged_*; the chain is described in ba_ragged_kernel.h) -------------------------------
+static_assert(TFF_BA_MAX_N == tff::BA_CLASS_BOUND_2 && tff::ba_lds_bytes(TFF_BA_MAX_N) <= LDS_LIMIT && tff::ba_lds_bytes(TFF_BA_MAX_N + 1) > LDS_LIMIT,
+              "TFF_BA_MAX_N is the largest N whose ba_lds_bytes(N) fits the 160 KiB of LDS");
+static_assert(0 < tff::BA_CLASS_BOUND_0 && tff::BA_CLASS_BOUND_0 < tff::BA_CLASS_BOUND_1 && tff::BA_CLASS_BOUND_1 < tff::BA_CLASS_BOUND_2, "three classes");
+static_assert(TFF_ST_TOO_LARGE == tff::ST_TOO_LARGE && TFF_ST_BAD_OFFSETS == tff::ST_BAD_OFFSETS, "status codes");
+// the upper classes hold one or two wavefronts per CU: a grid of this many blocks walks their lists with a stride
+constexpr long BA_UPPER_CLASS_GRID = 8192;
+constexpr long BA_ONE_CLASS_MAX_B = 256;   // the CUs of an MI355X
+
+struct BaRaggedCall {                      // device pointers
+    const double* corresp; const int64_t* offsets; int64_t n_total; const uint8_t* mask; const double* calm; int64_t calm_stride;
+    const double* Rt2_in; const double* Rt3_in; const double* reconst0; int64_t B;
+    double* Rt2; double* Rt3; double* reconst; int32_t* iter; double* repr_err; int32_t* used; int32_t* status;
+};
+int check_ba_ragged(const void* corresp, const void* offsets, int64_t n_total, const void* calm, int64_t calm_stride, const void* Rt2_in, const void* Rt3_in,
+                    int64_t B, const void* Rt2, const void* Rt3) {
+    if (B < 0) return fail(TFF_E_INVALID, "negative batch size");
+    if (n_total < 0 || n_total > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "n_total must lie in [0, 2^31 - 1]");
+    if (calm_stride != 0 && calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
+    if (B > 0 && (!offsets || !calm || !Rt2_in || !Rt3_in || !Rt2 || !Rt3 || (n_total > 0 && !corresp))) return fail(TFF_E_INVALID, "null pointer");
+    return 0;
+}
+int launch_ba_ragged(tff_ctx* c, const BaRaggedCall& q) {
+    const size_t B = (size_t)q.B, nt = (size_t)q.n_total;
+    // the plan: coff (B int64) | m (B) | class lists (3 B) | class counts (3);  a masked call: packed (6) | rec0 (3) | rec_ws (3 doubles) | src (int32) per correspondence
+    TFF_TRY(c->ba_plan.reserve(B * sizeof(int64_t) + (4 * B + tff::BA_CLASSES) * sizeof(int32_t)));
+    if (q.mask) TFF_TRY(c->ba_pack.reserve(nt * (12 * sizeof(double) + sizeof(int32_t)) + 8));
+    tff::BaRaggedPlan p{};
+    p.offsets = (const long*)q.offsets; p.B = (long)q.B; p.n_total = (long)q.n_total; p.mask = q.mask;
+    // A launch lasts as long as its slowest item and the class launches follow one another on the stream, so classes pay only where a single launch
+    // would leave items waiting for a CU.  Up to BA_ONE_CLASS_MAX_B items are all resident at once even at one wavefront per CU: one launch, sized for
+    // TFF_BA_MAX_N (measured on the fountain and Herz-Jesu lists: 1.5 times faster than three).  B is a host value: no synchronisation.
+    const bool one_class = c->ba_classes == 1 || (c->ba_classes == 0 && q.B <= BA_ONE_CLASS_MAX_B);
+    p.bound[0] = one_class ? TFF_BA_MAX_N : tff::BA_CLASS_BOUND_0;
+    p.bound[1] = one_class ? TFF_BA_MAX_N : tff::BA_CLASS_BOUND_1;
+    p.bound[2] = TFF_BA_MAX_N;
+    p.coff = (long*)c->ba_plan.p;
+    p.m = (int*)(p.coff + B);
+    p.cls_list = p.m + B;
+    p.cls_count = p.cls_list + tff::BA_CLASSES * B;
+    p.corresp = q.corresp; p.reconst0 = q.reconst0;
+    double* rec_ws = nullptr;
+    if (q.mask) {
+        p.packed = (double*)c->ba_pack.p;
+        p.rec0 = p.packed + 6 * nt;
+        rec_ws = p.rec0 + 3 * nt;
+        p.src = (int*)(rec_ws + 3 * nt);
+    }
+    p.rec_ws = rec_ws;
+    p.Rt2 = q.Rt2; p.Rt3 = q.Rt3; p.reconst = q.reconst; p.iter = q.iter; p.repr_err = q.repr_err; p.used = q.used; p.status = q.status;
+    TFF_HIP(hipMemsetAsync(p.cls_count, 0, tff::BA_CLASSES * sizeof(int32_t), c->stream));
+    const unsigned per_item = (unsigned)(q.B < (1L << 20) ? q.B : (1L << 20)), per_thread = (unsigned)((q.B + 255) / 256);
+    TFF_TRY(launch(c, tff::k_ba_ragged_count, per_item, 64, 0, p));
+    if (q.mask) TFF_TRY(launch(c, tff::k_ba_ragged_scan, 1, tff::BA_RAGGED_SCAN_THREADS, 0, p));
+    TFF_TRY(launch(c, tff::k_ba_ragged_classes, per_thread, 256, 0, p));
+    if (q.mask) TFF_TRY(launch(c, tff::k_ba_ragged_compact, per_item, tff::BA_RAGGED_TILE, 0, p));
+    for (int k = 0; k < tff::BA_CLASSES; ++k) {
+        if (k > 0 && p.bound[k] == p.bound[k - 1]) continue;                 // (an empty class: the one-class plan)
+        const tff::BaArgs a = tff::ba_ragged_class_args(p, q.calm, (long)q.calm_stride, q.Rt2_in, q.Rt3_in, rec_ws, k);
+        const long grid = (k == 0 || q.B < BA_UPPER_CLASS_GRID) ? (long)tff::pose_grid(q.B) : BA_UPPER_CLASS_GRID;
+        TFF_TRY(launch(c, tff::k_bundle_adjust, (unsigned)grid, 64, tff::ba_lds_bytes(p.bound[k]), a));
+    }
+    if (q.reconst) TFF_TRY(launch(c, tff::k_ba_ragged_scatter, per_item, tff::BA_RAGGED_TILE, 0, p));
+    return 0;
+}
+
 // BundleAdjustment as the reference writes it, M = 2 .. 6 views, MATLAB's own array layouts (csrc/ba_views_kernel.h)
 template <int M>
 int launch_bundle_adjust_views(tff_ctx* c, const tff::BavArgs& a) {
@@ -1352,6 +1422,74 @@ int tff_bundle_adjust_batch_host(tff_ctx* c, const double* calm, int64_t calm_st
         TFF_HIP(hipMemcpyAsync(Rt3, d_o3, npose, hipMemcpyDeviceToHost, c->stream));
         return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
     });
+}
+
+// BundleAdjustment for a packed batch of items with different correspondence counts, optionally thinned by a mask (launch_ba_ragged above)
+int tff_bundle_adjust_ragged_dev(tff_ctx* c, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
+                                 int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3,
+                                 double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2_in, Rt3_in, B, Rt2, Rt3));
+    return run_batch(c, B, true, nullptr, &status, [&] {
+        return launch_ba_ragged(c, BaRaggedCall{corresp, offsets, n_total, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, reconst, iter, repr_err,
+                                                used, status});
+    });
+}
+int tff_bundle_adjust_ragged_host(tff_ctx* c, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm, int64_t calm_stride,
+                                  const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3, double* reconst,
+                                  int32_t* iter, double* repr_err, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    if (B < 0) return fail(TFF_E_INVALID, "negative batch size");
+    if (B > 0 && !offsets) return fail(TFF_E_INVALID, "null pointer");
+    if (B > 0 && offsets[0] < 0) return fail(TFF_E_INVALID, "offsets[0] must be >= 0");
+    for (int64_t b = 0; b < B; ++b) if (offsets[b + 1] < offsets[b]) return fail(TFF_E_INVALID, "offsets must not decrease");
+    const int64_t first = B > 0 ? offsets[0] : 0, n_total = B > 0 ? offsets[B] : 0;
+    TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2_in, Rt3_in, B, Rt2, Rt3));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        const size_t nb = (size_t)B, nt = (size_t)n_total, f = (size_t)first, cnt = nt - f;
+        const size_t nin = nt * 6 * sizeof(double), npt = nt * 3 * sizeof(double), npose = nb * 12 * sizeof(double);
+        const size_t ncal = (calm_stride ? nb : 1) * 27 * sizeof(double);
+        TFF_TRY(c->in.reserve(nin + npt + 2 * npose + 8));
+        TFF_TRY(c->calm.reserve(ncal));
+        TFF_TRY(c->out.reserve(2 * npose + npt + nb * sizeof(double) + 8));
+        TFF_TRY(c->idx.reserve(nb * 2 * sizeof(int32_t)));
+        TFF_TRY(c->ragged_off.reserve((nb + 1) * sizeof(int64_t)));
+        TFF_TRY(c->ba_host.reserve(nb * sizeof(int32_t) + nt + 8));
+        double* d_in = (double*)c->in.p;
+        double* d_x0 = d_in + 6 * nt;
+        double* d_r2 = d_x0 + 3 * nt;
+        double* d_r3 = d_r2 + 12 * nb;
+        double* d_o2 = (double*)c->out.p;
+        double* d_o3 = d_o2 + 12 * nb;
+        double* d_rec = d_o3 + 12 * nb;
+        double* d_err = d_rec + 3 * nt;
+        int32_t* d_iter = (int32_t*)c->idx.p;
+        int32_t* d_used = (int32_t*)c->ba_host.p;
+        uint8_t* d_mask = (uint8_t*)(d_used + nb);
+        if (cnt) TFF_HIP(hipMemcpyAsync(d_in + 6 * f, corresp + 6 * f, cnt * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (reconst0 && cnt) TFF_HIP(hipMemcpyAsync(d_x0 + 3 * f, reconst0 + 3 * f, cnt * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (mask && cnt) TFF_HIP(hipMemcpyAsync(d_mask + f, mask + f, cnt, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r2, Rt2_in, npose, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r3, Rt3_in, npose, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(c->ragged_off.p, offsets, (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_ba_ragged(c, BaRaggedCall{d_in, (const int64_t*)c->ragged_off.p, n_total, mask ? d_mask : nullptr, (const double*)c->calm.p, calm_stride, d_r2, d_r3,
+                                                 reconst0 ? d_x0 : nullptr, B, d_o2, d_o3, reconst ? d_rec : nullptr, d_iter, d_err, d_used, d_iter + nb}));
+        TFF_HIP(hipMemcpyAsync(Rt2, d_o2, npose, hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipMemcpyAsync(Rt3, d_o3, npose, hipMemcpyDeviceToHost, c->stream));
+        if (reconst && cnt) TFF_HIP(hipMemcpyAsync(reconst + 3 * f, d_rec + 3 * f, cnt * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (iter) TFF_HIP(hipMemcpyAsync(iter, d_iter, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (repr_err) TFF_HIP(hipMemcpyAsync(repr_err, d_err, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (used) TFF_HIP(hipMemcpyAsync(used, d_used, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (status) TFF_HIP(hipMemcpyAsync(status, d_iter + nb, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]) {
+    if (!bounds) return fail(TFF_E_INVALID, "null pointer");
+    bounds[0] = tff::BA_CLASS_BOUND_0; bounds[1] = tff::BA_CLASS_BOUND_1; bounds[2] = tff::BA_CLASS_BOUND_2;
+    return 0;
 }
 
 // BundleAdjustment as the reference writes it, M = 2 .. 6 views (launch_bundle_adjust_views above)
