@@ -441,8 +441,16 @@ int tff_pose_batch_dev_multi(tff_multi* m, int32_t method, const double* const* 
  * Each triplet's outputs are bit-identical to those of the fixed-N entry point of the method called on that triplet alone, under the same
  * context options: triplet b takes the kernels the fixed-N call takes for n_b (TFF_ST_TOO_FEW below 7 / 8 correspondences, the exact tiers
  * below TFF_OPT_EXACT_BELOW or with TFF_OPT_SOLVER = 1, the exact fix-up of what the fast tiers flag), and writes what that call writes,
- * its Reconst range included.  Methods: TFF_METHOD_LINEAR_TFT and TFF_METHOD_LINEAR_F (others: TFF_E_INVALID).  TFF_OPT_PRE is ignored
- * (the moments come from the row kernels' own passes, the default); TFF_OPT_ROWS = 0 and TFF_OPT_KERNEL = 1 give TFF_E_INVALID.
+ * its Reconst range included.  Methods: TFF_METHOD_LINEAR_TFT, TFF_METHOD_LINEAR_F and TFF_METHOD_OPTIM_F (others: TFF_E_INVALID).
+ * TFF_OPT_PRE is ignored (the moments come from the row kernels' own passes, the default); TFF_OPT_ROWS = 0 and TFF_OPT_KERNEL = 1 give
+ * TFF_E_INVALID.
+ * TFF_METHOD_OPTIM_F: an item with n_b < max(8, TFF_OPT_EXACT_BELOW), or any item with TFF_OPT_SOLVER = 1, is done whole by the one-triplet
+ * exact kernel (TFF_ST_TOO_FEW below 8); the others take the three staged kernels of the fixed-N call (linear stage, Gauss-Helmert
+ * refinement, pose tail), then the exact kernel over what those flag; iter = it1 + it2.  The refinement runs as up to three launches by n_b:
+ * observations and estimates in LDS up to bounds[0], the estimates alone in LDS up to bounds[1], the estimates in global slices beyond
+ * (tff_optim_f_ragged_bounds; TFF_OPT_SPILL moves bounds[1] as it does for the fixed-N call).  Every item takes the storage route its
+ * fixed-N call takes, whatever n_max and its neighbours are.  Workspaces, grown on demand: a record of 32 doubles per item, the slices
+ * (only when n_max exceeds bounds[1]: one of 4 n_max + 16 doubles per resident wavefront), the plan and the retry list (B + 2 int32).
  * _dev: device pointers, offsets included; n_max (host) bounds every n_b (at most 2^24) and sizes the plan's workspace: the plan keeps
  * three int32 per n in 0 .. n_max and scans them in one workgroup, so its cost grows with n_max, not with B (n_max = 2^24: ~200 MB and a
  * scan of 16 M buckets per call) -- pass a bound close to the largest n_b; an item that breaks
@@ -457,6 +465,11 @@ int tff_pose_batch_ragged_dev(tff_ctx* ctx, int32_t method, const double* corres
 int tff_pose_batch_ragged_host(tff_ctx* ctx, int32_t method, const double* corresp, const int64_t* offsets, const double* calm,
                                int64_t calm_stride, int64_t B, double* Rt2, double* Rt3, double* T, double* reconst, int32_t* iter,
                                int32_t* status);
+/* TFF_METHOD_OPTIM_F in a ragged call: bounds[0] = the largest n whose refinement keeps the normalised observations in LDS (the largest n with
+ * optimf_refine_lds_bytes(n, true) + 512 <= 160 KiB / 8, where optimf_refine_lds_bytes(n, staged) = 8 (F + 4 n + 2 + (staged ? 6 n : 0)) for a
+ * fixed part of F doubles), bounds[1] = the largest n whose estimates stay in LDS under the default options (the largest n with
+ * 160 KiB / (optimf_refine_lds_bytes(n, false) + 512) >= 8).  Computed from the expressions the launchers use; 0 < bounds[0] < bounds[1]. */
+int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,7 @@ def load_library(path=None):
             "tff_bundle_adjust_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_class_bounds": [V],
+            "tff_optim_f_ragged_bounds": [V],
         }
         for name, sig in protos.items():
             fn = getattr(lib, name)
@@ -171,6 +172,7 @@ EXPORTED_SYMBOLS = [
     "tff_sample_indices_dev", "tff_inlier_mask_batch_dev", "tff_robust_pose_dev", "tff_robust_pose_host",
     "tff_robust_pose_scenes_dev", "tff_robust_pose_scenes_host", "tff_inlier_count_scenes_dev",
     "tff_bundle_adjust_ragged_dev", "tff_bundle_adjust_ragged_host", "tff_bundle_adjust_ragged_class_bounds",
+    "tff_optim_f_ragged_bounds",
 ]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
@@ -179,7 +181,7 @@ METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "Nordbe
 
 
 # methods a ragged call (Context.pose_batch_ragged) supports
-RAGGED_METHODS = ("LinearTFTPoseEstimation", "LinearFPoseEstimation")
+RAGGED_METHODS = ("LinearTFTPoseEstimation", "LinearFPoseEstimation", "OptimFPoseEstimation")
 
 
 # methods the robust estimator (Context.robust_pose) draws its hypotheses and refits with, and their minimal sample
@@ -258,6 +260,16 @@ def ba_ragged_class_bounds():
     lib = load_library()
     b = (ctypes.c_int32 * 3)()
     _check(lib, lib.tff_bundle_adjust_ragged_class_bounds(b), "tff_bundle_adjust_ragged_class_bounds")
+    return tuple(int(v) for v in b)
+
+
+def optim_f_ragged_bounds():
+    """tff_optim_f_ragged_bounds: (S, L), the largest correspondence counts at which the Gauss-Helmert refinement of OptimFPoseEstimation keeps the
+    normalised observations in LDS (S) and its estimates in LDS under the default options (L): the boundaries of the three launch classes of
+    Context.pose_batch_ragged("OptimFPoseEstimation", ...), and of the fixed-N call's storage routes."""
+    lib = load_library()
+    b = (ctypes.c_int32 * 2)()
+    _check(lib, lib.tff_optim_f_ragged_bounds(b), "tff_optim_f_ragged_bounds")
     return tuple(int(v) for v in b)
 
 
@@ -445,12 +457,13 @@ class Context:
 
 
     def pose_batch_ragged(self, method, corresp, offsets, calm, reconst=True, n_max=None):
-        """One call for triplets with different correspondence counts (LinearTFT, LinearF): corresp (Ntot, 6) packed, offsets (B + 1,)
+        """One call for triplets with different correspondence counts (LinearTFT, LinearF, OptimF): corresp (Ntot, 6) packed, offsets (B + 1,)
         int64 with triplet b = corresp[offsets[b]:offsets[b + 1]] (see pack_ragged); calm (9, 3) shared or (B, 9, 3).  Each triplet's
         outputs are bit-identical to pose_batch() on that triplet alone.  numpy in -> numpy out (host path; malformed offsets raise).
         torch CUDA tensors in (offsets on the same device) -> torch tensors out, asynchronous on the current stream; n_max bounds every
         n_b (a larger one marks the item ST_BAD_OFFSETS) -- pass it to avoid the one synchronisation that computes it from the offsets.
-        Returns dict(R_t_2 (B,3,4), R_t_3 (B,3,4), T (B,3,3,3), Reconst (Ntot,3) packed or None, iter (B,), status (B,))."""
+        Returns dict(R_t_2 (B,3,4), R_t_3 (B,3,4), T (B,3,3,3), Reconst (Ntot,3) packed or None, iter (B,), status (B,)); iter carries the
+        Gauss-Helmert counts of OptimF (0 for the linear methods)."""
         if method not in METHOD_IDS:
             raise ValueError("unknown method %r" % (method,))
         mid = METHOD_IDS[method]
@@ -696,6 +709,11 @@ class Context:
         return dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec, iter=it, repr_err=err, used=used,
                     status=st)
 
+    @staticmethod
+    def _refined(out, r):
+        """the refine step of robust_pose_scenes: the outputs of its one pose_batch_ragged call under their names"""
+        out.update(R_t_2_refined=r["R_t_2"], R_t_3_refined=r["R_t_3"], T_refined=r["T"], iter_refined=r["iter"], status_refined=r["status"])
+
     def _polish(self, out, calm, scenes, offsets, single):
         """the polish of robust_pose / robust_pose_scenes: ONE bundle_adjust_ragged call on the result's poses and mask"""
         r2, r3 = out["R_t_2"], out["R_t_3"]
@@ -848,7 +866,7 @@ class Context:
         return calm_cm.to(device=dev, dtype=torch.float64), stride
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
-                           polish=False):
+                           polish=False, refine=None):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
@@ -856,7 +874,13 @@ class Context:
         scene's size, is passed (it is computed from the offsets with one synchronisation otherwise); a scene with bad offsets or fewer correspondences than a
         sample gets ST_BAD_OFFSETS / ST_TOO_FEW.  numpy in -> numpy out through the _host form, which refuses malformed offsets.
         polish=True: BundleAdjustment on every scene's pose and inliers in ONE more call (bundle_adjust_ragged on the result's poses and mask), as
-        R_t_2_polished, R_t_3_polished (S,3,4), iter_polished, repr_err_polished, status_polished (S,); a scene without a pose gets ST_TOO_FEW there."""
+        R_t_2_polished, R_t_3_polished (S,3,4), iter_polished, repr_err_polished, status_polished (S,); a scene without a pose gets ST_TOO_FEW there.
+        refine = a name in RAGGED_METHODS: that method on every scene's inliers in ONE pose_batch_ragged call (reconst=False), as R_t_2_refined, R_t_3_refined
+        (S,3,4), T_refined (S,3,3,3), iter_refined, status_refined (S,): bit for bit what robust_pose(..., refine=...) gives for the scene alone; a scene
+        without a pose has no inliers and gets ST_TOO_FEW and NaN.  On the device path the inliers are packed without reading a count (no
+        synchronisation when ns_max is passed).  The polish keeps starting from the robust poses."""
+        if refine is not None and refine not in RAGGED_METHODS:
+            raise ValueError("robust_pose_scenes refines with one of %s, not %r" % (", ".join(RAGGED_METHODS), refine))
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose_scenes draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         mid = METHOD_IDS[method]
@@ -882,6 +906,11 @@ class Context:
             out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
                        T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
                        candidates=info[:, 3], status=st)
+            if refine is not None:
+                keep = mask != 0
+                inl = np.ascontiguousarray(sc[keep])
+                cum = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+                self._refined(out, self.pose_batch_ragged(refine, inl, cum[offsets], calm, reconst=False))
             return self._polish(out, calm, sc, offsets, False) if polish else out
         if not (isinstance(scenes, torch.Tensor) and scenes.is_cuda and scenes.dtype == torch.float64 and scenes.is_contiguous() and scenes.dim() == 2
                 and scenes.shape[1] == 6):
@@ -906,6 +935,13 @@ class Context:
                                                              self._p(st)), "tff_robust_pose_scenes_dev")
         out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
                    mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        if refine is not None:
+            # every scene's inliers first, in scene order, without reading a count: a stable sort of 1 - mask; all Ntot rows are kept, the offsets say
+            # where the inliers end (boolean indexing and nonzero would synchronise)
+            keep = (mask != 0).to(torch.int64)
+            packed = scenes[torch.argsort(1 - keep, stable=True)]
+            cum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(keep, 0)])
+            self._refined(out, self.pose_batch_ragged(refine, packed, cum[offsets.clamp(0, ntot)], calm, reconst=False, n_max=int(ns_max)))
         return self._polish(out, calm, scenes, offsets, False) if polish else out
 
     def inlier_count_scenes(self, scenes, offsets, calm, R_t_2, R_t_3, threshold=1.0):

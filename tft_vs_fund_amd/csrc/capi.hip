@@ -226,20 +226,30 @@ unsigned fixup_grid(int64_t B, long resident = FIXUP_GRID) { return (unsigned)(B
 // occupancy_cap > 0 (the workgroup kernels; the cap is what their registers allow): spill also when that lets more workgroups share
 // the CU's LDS -- their wave-serial steps (KKT solve, pseudo-inverse) make workgroups per CU what counts.  Measured
 // (tools/bench_n_sweep.py): Ressl 2.14 -> 3.26 M/s at N = 500, Pi 1.18 -> 1.79 M/s at N = 300, never slower.
-int plan_spill(tff_ctx* c, size_t lds_full, size_t lds_fixed, unsigned* grid, double** spill, long* stride, size_t* lds, int occupancy_cap = 0) {
-    *spill = nullptr; *stride = 0; *lds = lds_full;
+// the decision alone (no context: tff_optim_f_ragged_bounds evaluates it too)
+bool spill_wanted(bool only_if_needed, size_t lds_full, size_t lds_fixed, int occupancy_cap) {
     auto per_cu = [&](size_t bytes) { const size_t k = LDS_LIMIT / (bytes + 512); return (int)(k < (size_t)occupancy_cap ? k : (size_t)occupancy_cap); };
-    const bool for_occupancy = !c->spill_only_if_needed && occupancy_cap > 0 && lds_fixed < lds_full && per_cu(lds_fixed) > per_cu(lds_full);
-    if (lds_full <= LDS_LIMIT && !for_occupancy) return 0;
-    if (lds_fixed > LDS_LIMIT) return fail(TFF_E_INVALID, "LDS workspace of this method exceeds 160 KiB");
-    // + 16 doubles: the kernels carve their per-correspondence arrays with small alignment pads (e.g. OptimF's v = xi + 4N + 2), so a
-    // slice of exactly lds_full - lds_fixed bytes would let the tail of one block's arrays overlap the head of its neighbour's
-    const size_t per_block = lds_full - lds_fixed + 16 * sizeof(double);
+    const bool for_occupancy = !only_if_needed && occupancy_cap > 0 && lds_fixed < lds_full && per_cu(lds_fixed) > per_cu(lds_full);
+    return lds_full > LDS_LIMIT || for_occupancy;
+}
+// the slices: state_bytes per block + 16 doubles -- the kernels carve their per-correspondence arrays with small alignment pads (e.g. OptimF's
+// v = xi + 4N + 2), so a slice of exactly state_bytes would let the tail of one block's arrays overlap the head of its neighbour's.  The grid is
+// capped at the number of slices.
+int spill_slices(tff_ctx* c, size_t state_bytes, unsigned* grid, double** spill, long* stride) {
+    const size_t per_block = state_bytes + 16 * sizeof(double);
     size_t blocks = ((size_t)512 << 20) / per_block;
     if (blocks < 256) blocks = 256;
     if (*grid > blocks) *grid = (unsigned)blocks;
     TFF_TRY(c->spill.reserve((size_t)*grid * per_block));
-    *spill = (double*)c->spill.p; *stride = (long)(per_block / sizeof(double)); *lds = lds_fixed;
+    *spill = (double*)c->spill.p; *stride = (long)(per_block / sizeof(double));
+    return 0;
+}
+int plan_spill(tff_ctx* c, size_t lds_full, size_t lds_fixed, unsigned* grid, double** spill, long* stride, size_t* lds, int occupancy_cap = 0) {
+    *spill = nullptr; *stride = 0; *lds = lds_full;
+    if (!spill_wanted(c->spill_only_if_needed != 0, lds_full, lds_fixed, occupancy_cap)) return 0;
+    if (lds_fixed > LDS_LIMIT) return fail(TFF_E_INVALID, "LDS workspace of this method exceeds 160 KiB");
+    TFF_TRY(spill_slices(c, lds_full - lds_fixed, grid, spill, stride));
+    *lds = lds_fixed;
     return 0;
 }
 
@@ -326,6 +336,13 @@ int launch_linear_f(tff_ctx* c, const PoseCall& p) {
 // OptimFPoseEstimation.  Three stages (optimf_rows_kernel.h) -- linear stage and pose tail four triplets per wavefront, the Gauss-Helmert
 // refinement one wavefront per triplet -- then the exact kernel over what they could not finish.  Minimal samples, TFF_OPT_ROWS = 0,
 // TFF_OPT_SOLVER = 1, TFF_OPT_KERNEL = 1, debug records: the fused one-triplet kernel.
+// k_optimf_refine's storage of N correspondences, as the fixed-N launcher picks it (the ragged launcher's classes and tff_optim_f_ragged_bounds
+// follow the same two rules).  The normalised observations go to LDS with xi while eight wavefronts still fit a CU (N <= ~220); beyond, the passes
+// read the correspondences through L2 as the fused kernel does, and xi follows plan_spill's occupancy rule.
+bool optimf_stage_x(int N) { return tff::optimf_refine_lds_bytes(N, true) + 512 <= LDS_LIMIT / (4 * tff::OPTIMF_REFINE_WAVES); }
+bool optimf_xi_in_lds(bool spill_only_if_needed, int N) {
+    return !spill_wanted(spill_only_if_needed, tff::optimf_refine_lds_bytes(N, false), tff::optimf_refine_lds_bytes(0, false), 4 * tff::OPTIMF_REFINE_WAVES);
+}
 int launch_optim_f(tff_ctx* c, const PoseCall& p) {
     const bool staged_route = use_rows(c) && fast_tiers(c, p.N) && p.N >= 8 && !p.dbg && !p.sample_idx && c->kernel_variant != 1;
     if (staged_route) {
@@ -339,10 +356,7 @@ int launch_optim_f(tff_ctx* c, const PoseCall& p) {
             tff::OptimFStageArgs m = sa;
             unsigned grid = tff::pose_grid(p.B);
             size_t lds;
-            // the normalised observations go to LDS with xi while eight wavefronts still fit a CU (N <= ~220); beyond, the passes read the correspondences
-            // through L2 as the fused kernel does, and xi follows plan_spill's occupancy rule
-            const bool stage_x = tff::optimf_refine_lds_bytes(N, true) + 512 <= LDS_LIMIT / (4 * tff::OPTIMF_REFINE_WAVES);
-            if (stage_x) {
+            if (optimf_stage_x(N)) {
                 TFF_TRY(launch(c, tff::k_optimf_refine<tff::OPTIMF_REFINE_WAVES, true>, grid, 64, tff::optimf_refine_lds_bytes(N, true), m));
             } else {
                 TFF_TRY(plan_spill(c, tff::optimf_refine_lds_bytes(N, false), tff::optimf_refine_lds_bytes(0, false), &grid, &m.spill, &m.spill_stride, &lds, 4 * tff::OPTIMF_REFINE_WAVES));
@@ -465,11 +479,13 @@ int launch_pi(tff_ctx* c, const PoseCall& p) { return launch_pi_model<tff::PiMod
 int launch_picol(tff_ctx* c, const PoseCall& p) { return launch_pi_model<tff::PiColModel>(c, p); }
 
 // ---- the methods ----------------------------------------------------------------------------------------------------------------------------
-struct RaggedRoute {                       // the kernels of one method's ragged chain (fast == nullptr: the method has none)
-    pose_kernel fast, exact, fixup;
+struct RaggedRoute {                       // the kernels of one method's ragged chain (row kernel of the fast tiers, of the exact tiers, fix-up), or, for a
+    pose_kernel fast, exact, fixup;        // chain of more stages, a launcher of its own (both null: the method has none)
     lds_fn fix_lds;
     int stage_max_n;
+    pose_launcher chain = nullptr;
 };
+int launch_ragged_optim_f(tff_ctx* c, const PoseCall& p);
 struct Method {
     pose_launcher launch;
     RaggedRoute ragged;
@@ -484,7 +500,7 @@ const Method METHODS[] = {                 // indexed by TFF_METHOD_*
     {launch_picol, {}},
     {launch_linear_f, {tff::k_linear_f_pose_rows_ragged, tff::k_linear_f_pose_rows_exact_ragged, tff::k_f_pose<true, 0, true>,
                        tff::f_pose_lds_bytes, tff::STAGE_MAX_N_F}},
-    {launch_optim_f, {}},
+    {launch_optim_f, {nullptr, nullptr, nullptr, nullptr, 0, launch_ragged_optim_f}},
 };
 static_assert(TFF_METHOD_LINEAR_TFT == 0 && TFF_METHOD_RESSL_TFT == 1 && TFF_METHOD_NORDBERG_TFT == 2 && TFF_METHOD_FAUGPAPA_TFT == 3 && TFF_METHOD_PI == 4 &&
               TFF_METHOD_PICOL == 5 && TFF_METHOD_LINEAR_F == 6 && TFF_METHOD_OPTIM_F == 7 && sizeof(METHODS) / sizeof(METHODS[0]) == 8, "METHODS follows the ids");
@@ -562,7 +578,8 @@ int ragged_route(const tff_ctx* c, int32_t method, const RaggedRoute** route) {
     if (!use_rows(c)) return fail(TFF_E_INVALID, "ragged batches run on the row kernels: TFF_OPT_ROWS = 0 is not supported");
     if (c->kernel_variant == 1) return fail(TFF_E_INVALID, "ragged batches: TFF_OPT_KERNEL = 1 (fused single-wavefront kernels) is not supported");
     *route = &method_of(method)->ragged;
-    if (!(*route)->fast) return fail(TFF_E_INVALID, "ragged batches are implemented for LinearTFT and LinearF only; group this method's triplets by N");
+    if (!(*route)->fast && !(*route)->chain)
+        return fail(TFF_E_INVALID, "ragged batches are implemented for LinearTFT, LinearF and OptimF only; group this method's triplets by N");
     return 0;
 }
 int check_ragged(const tff_ctx* c, int32_t method, const PoseCall& p, const RaggedRoute** route) {
@@ -589,21 +606,35 @@ int ragged_stage_upto(const tff_ctx* c, const RaggedRoute& r, int flags, int32_t
     return lo;
 }
 
+// the plan on the stream: hist | fill | start (n_max + 1 each) | route (RAGGED_ROUTE_INTS) | slot list.  *pa: offsets, B, n_max, split, cut and the retry
+// list are the caller's; the workspace pointers and outputs are filled in here.
+int launch_ragged_plan(tff_ctx* c, const PoseCall& p, tff::RaggedPlanArgs* pa, long* slots) {
+    const size_t nb = (size_t)p.N + 1;
+    *slots = tff::ragged_slots((long)p.B, p.N);
+    TFF_TRY(c->ragged.reserve((3 * nb + tff::RAGGED_ROUTE_INTS + (size_t)*slots) * sizeof(int32_t)));
+    int* ws = (int*)c->ragged.p;
+    pa->offsets = (const long*)p.offsets; pa->B = (long)p.B; pa->n_max = p.N;
+    pa->hist = ws; pa->fill = ws + nb; pa->start = ws + 2 * nb; pa->route = ws + 3 * nb; pa->list = ws + 3 * nb + tff::RAGGED_ROUTE_INTS;
+    pa->Rt2 = p.Rt2; pa->Rt3 = p.Rt3; pa->T = p.T; pa->iter = p.iter; pa->status = p.status;
+    TFF_HIP(hipMemsetAsync(ws, 0, 2 * nb * sizeof(int32_t), c->stream));
+    const unsigned items = (unsigned)((p.B + 255) / 256);
+    TFF_TRY(launch(c, tff::k_ragged_count, items, 256, 0, *pa));
+    TFF_TRY(launch(c, tff::k_ragged_scan, 1, tff::RAGGED_SCAN_THREADS, 0, *pa));
+    return launch(c, tff::k_ragged_scatter, items, 256, 0, *pa);
+}
+int ragged_split(const tff_ctx* c, int32_t n_max, int least) {
+    const int at = c->exact_below > least ? c->exact_below : least;
+    return (c->solver != 0 || at > n_max) ? n_max + 1 : at;
+}
+
 int launch_ragged(tff_ctx* c, const RaggedRoute& r, const PoseCall& p) {
+    if (r.chain) return r.chain(c, p);
     const int64_t B = p.B;
     const int32_t n_max = p.N;
-    // the plan: hist | fill | start (n_max + 1 each) | route (4) | slot list
-    const size_t nb = (size_t)n_max + 1;
-    const long slots = tff::ragged_slots((long)B, n_max);
-    TFF_TRY(c->ragged.reserve((3 * nb + 4 + (size_t)slots) * sizeof(int32_t)));
-    int* ws = (int*)c->ragged.p;
-    tff::RaggedPlanArgs pa{(const long*)p.offsets, (long)B, n_max, 0, ws, ws + nb, ws + 2 * nb, ws + 3 * nb, ws + 3 * nb + 4, p.Rt2, p.Rt3, p.T, p.iter, p.status};
-    pa.split = (c->solver != 0 || c->exact_below > n_max) ? n_max + 1 : (c->exact_below > 0 ? c->exact_below : 0);
-    TFF_HIP(hipMemsetAsync(ws, 0, 2 * nb * sizeof(int32_t), c->stream));
-    const unsigned items = (unsigned)((B + 255) / 256);
-    TFF_TRY(launch(c, tff::k_ragged_count, items, 256, 0, pa));
-    TFF_TRY(launch(c, tff::k_ragged_scan, 1, tff::RAGGED_SCAN_THREADS, 0, pa));
-    TFF_TRY(launch(c, tff::k_ragged_scatter, items, 256, 0, pa));
+    tff::RaggedPlanArgs pa{};
+    pa.split = ragged_split(c, n_max, 0);
+    long slots;
+    TFF_TRY(launch_ragged_plan(c, p, &pa, &slots));
     tff::LinearTftArgs a{p.corresp, p.calm, (long)p.calm_stride, (long)B, 0, base_flags(c, p.reconst != nullptr), p.Rt2, p.Rt3, p.T, p.reconst, p.iter, p.status};
     TFF_TRY(retry_list_begin(c, &a));
     a.offsets = (const long*)p.offsets;
@@ -624,6 +655,103 @@ int launch_ragged(tff_ctx* c, const RaggedRoute& r, const PoseCall& p) {
     a.stage_upto = ragged_stage_upto(c, r, a.flags, n_max);
     const size_t lds = a.stage_upto >= 0 ? r.fix_lds(a.stage_upto, a.flags | tff::FLAG_STAGE_LDS, true) : r.fix_lds(0, a.flags, true);
     return launch_retry_fixup(c, r.fixup, lds, a);
+}
+
+// largest n <= n_max with pred(n), pred holding for every n up to some bound; -1 if not even pred(0)
+template <class Pred>
+int largest_n(int n_max, Pred pred) {
+    if (!pred(0)) return -1;
+    int lo = 0, hi = n_max;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (pred(mid)) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the two bounds of k_optimf_refine's storage routes (launch_optim_f): observations staged in LDS up to [0], xi in LDS up to [1]
+void optimf_ragged_bounds(bool spill_only_if_needed, int32_t bounds[2]) {
+    bounds[0] = largest_n(RAGGED_MAX_N, optimf_stage_x);
+    bounds[1] = largest_n(RAGGED_MAX_N, [&](int n) { return optimf_xi_in_lds(spill_only_if_needed, n); });
+    if (bounds[1] < bounds[0]) bounds[1] = bounds[0];
+}
+
+// OptimFPoseEstimation, ragged.  Item b takes launch_optim_f's chain for N = n_b:
+//   n_b < max(8, exact_below) or TFF_OPT_SOLVER = 1   the plan marks it ST_RETRY and lists it: k_f_pose<true, 1, true> does it whole (n_b < 8: ST_TOO_FEW)
+//   otherwise                                         k_optimf_linear_rows_ragged -> k_optimf_refine<., ., true> -> k_optimf_finish_rows_ragged over the
+//                                                     slots [mid, total), then k_f_pose<true, 1, true> over what they marked ST_RETRY
+// The refinement runs as up to three launches over contiguous ranges of the slot list (it is sorted by n), each with the storage route and so the
+// kernel instance the fixed-N launcher picks for every n of its range: STAGE_X up to bounds[0], xi in LDS up to bounds[1], xi in global slices
+// beyond (slices sized for n_max).  An LDS request is sized for the largest n its range can hold, so the small items keep their eight wavefronts
+// per CU whatever n_max is.  A range the host knows to be empty is not launched; one that is empty on the device costs an empty launch.
+// Workspaces (grown on demand): gh_rec B x OPTIMF_REC_DOUBLES (indexed by item), spill (slices x (4 n_max + 16) doubles, only when n_max is beyond
+// the LDS bounds), ragged (the plan), retry.
+int launch_ragged_optim_f(tff_ctx* c, const PoseCall& p) {
+    const int64_t B = p.B;
+    const int32_t n_max = p.N;
+    int32_t bounds[2];
+    optimf_ragged_bounds(c->spill_only_if_needed != 0, bounds);
+    tff::OptimFStageArgs sa{};
+    sa.la = tff::LinearTftArgs{p.corresp, p.calm, (long)p.calm_stride, (long)B, 0, base_flags(c, p.reconst != nullptr), p.Rt2, p.Rt3, p.T, p.reconst, p.iter, p.status};
+    tff::LinearTftArgs& a = sa.la;
+    TFF_TRY(retry_list_begin(c, &a));
+    tff::RaggedPlanArgs pa{};
+    pa.split = ragged_split(c, n_max, 8);
+    const auto cut_at = [&](int upto, int least) { const long k = (long)upto + 1 > least ? (long)upto + 1 : least; return (int)(k > n_max ? (long)n_max + 1 : k); };
+    pa.cut[0] = cut_at(bounds[0], pa.split);
+    pa.cut[1] = cut_at(bounds[1], pa.cut[0]);
+    pa.retry_list = a.retry_list; pa.retry_count = a.retry_count;
+    // Every workspace is reserved before the plan goes on the stream: its scatter already appends to this call's retry counter, and only the linear
+    // stage below zeroes the other one, so nothing that can fail may come between the two.  Both users of the spill slices are sized together (the
+    // workspace is shared and must not move under the first of them).  All of it needs B, n_max and the slot count's upper bound only.
+    long slots = tff::ragged_slots((long)B, n_max);
+    const bool refine_spills = pa.cut[1] <= n_max;
+    const size_t fix_full = tff::optimf_lds_bytes(n_max, a.flags, true), fix_fixed = tff::optimf_lds_bytes(0, a.flags, true);
+    const bool fix_spills = fix_full > LDS_LIMIT;
+    unsigned grid_c = tff::pose_grid(slots), grid_fix = fixup_grid(B, 2 * FIXUP_GRID);
+    double* slices = nullptr; long stride = 0;
+    if (refine_spills || fix_spills) {     // one slice per block of the larger of the two grids, stride sized for n_max; the grids are capped at the slice count
+        unsigned need = 1;
+        if (refine_spills) need = grid_c;
+        if (fix_spills && grid_fix > need) need = grid_fix;
+        TFF_TRY(spill_slices(c, 4 * (size_t)n_max * sizeof(double), &need, &slices, &stride));
+        if (grid_c > need) grid_c = need;
+        if (grid_fix > need) grid_fix = need;
+    }
+    TFF_TRY(c->gh_rec.reserve((size_t)B * tff::OPTIMF_REC_DOUBLES * sizeof(double)));
+    sa.rec = (double*)c->gh_rec.p;
+    TFF_TRY(launch_ragged_plan(c, p, &pa, &slots));
+    a.offsets = (const long*)p.offsets;
+    a.rlist = pa.list;
+    a.stage_upto = -1;
+    const unsigned rows = tff::rows_grid(slots);
+    a.rrange = pa.route + 2;
+    TFF_TRY(launch(c, tff::k_optimf_linear_rows_ragged, rows, 64, tff::rows_lds_bytes(), sa));   // (always: it zeroes the next call's retry counter)
+    c->retry_parity ^= 1;
+    if (pa.split <= n_max) {
+        constexpr int W = tff::OPTIMF_REFINE_WAVES;
+        tff::OptimFStageArgs m = sa;
+        if (pa.split < pa.cut[0]) {
+            m.la.rrange = pa.route + 4;
+            m.lds_n = pa.cut[0] - 1;
+            TFF_TRY(launch(c, tff::k_optimf_refine<W, true, true>, tff::pose_grid(slots), 64, tff::optimf_refine_lds_bytes(m.lds_n, true), m));
+        }
+        if (pa.cut[0] < pa.cut[1]) {
+            m.la.rrange = pa.route + 6;
+            m.lds_n = pa.cut[1] - 1;
+            TFF_TRY(launch(c, tff::k_optimf_refine<W, false, true>, tff::pose_grid(slots), 64, tff::optimf_refine_lds_bytes(m.lds_n, false), m));
+        }
+        if (refine_spills) {
+            m.la.rrange = pa.route + 8;
+            m.lds_n = 0;
+            m.spill = slices; m.spill_stride = stride;
+            TFF_TRY(launch(c, tff::k_optimf_refine<W, false, true>, grid_c, 64, tff::optimf_refine_lds_bytes(0, false), m));
+        }
+        TFF_TRY(launch(c, tff::k_optimf_finish_rows_ragged, rows, 64, tff::rows_lds_bytes(), sa));
+    }
+    a.rrange = nullptr;
+    a.flags |= tff::FLAG_ONLY_RETRY;
+    if (fix_spills) { a.spill = slices; a.spill_stride = stride; }
+    return launch(c, tff::k_f_pose<true, 1, true>, grid_fix, 64, fix_spills ? fix_fixed : fix_full, a);
 }
 
 // ---- inlier counts and flags of pose hypotheses against one shared scene ------------------------------------------------------------------------
@@ -1489,6 +1617,12 @@ int tff_bundle_adjust_ragged_host(tff_ctx* c, const double* corresp, const int64
 int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]) {
     if (!bounds) return fail(TFF_E_INVALID, "null pointer");
     bounds[0] = tff::BA_CLASS_BOUND_0; bounds[1] = tff::BA_CLASS_BOUND_1; bounds[2] = tff::BA_CLASS_BOUND_2;
+    return 0;
+}
+
+int tff_optim_f_ragged_bounds(int32_t bounds[2]) {
+    if (!bounds) return fail(TFF_E_INVALID, "null pointer");
+    optimf_ragged_bounds(false, bounds);
     return 0;
 }
 

@@ -12,6 +12,13 @@
 // itself keeps per-correspondence state and gains nothing from the row layout (built, measured, not kept).  With the
 // stages split each runs in the layout that suits it.  A triplet a fast tier cannot finish anywhere is marked ST_RETRY and redone whole by
 // k_f_pose<true, 1>.
+//
+// Ragged batches (the <RAGGED = true> forms; plan in ragged_kernel.h): the two row kernels walk the slots [mid, total) of the bucket list as
+// linear_f_pose_rows<true> does; the refinement walks one of up to three ranges of it, one wavefront per slot entry, each range with the storage
+// route the fixed-N launcher picks for its n (STAGE_X | xi in LDS | xi in a global slice) and an LDS request sized for the range's largest n.
+// Statuses: an item with n < split (the exact tiers, and n < 8) is never walked by these kernels -- its status is first written by
+// k_ragged_scatter (ST_RETRY, with its entry of the retry list); every other valid item's by k_optimf_linear_rows.  All three kernels append
+// what they mark ST_RETRY to the retry list (an item at most once: the later stages skip it), which k_f_pose<true, 1, true> walks.
 // Reference: F_methods/OptimFPoseEstimation.m:44-73, F_methods/optimF.m:34-109.
 #pragma once
 #include "f_rows_kernel.h"
@@ -28,18 +35,21 @@ struct OptimFStageArgs {
     LinearTftArgs la;
     double* rec;             // B x OPTIMF_REC_DOUBLES
     double* spill; long spill_stride;   // k_optimf_refine: per-correspondence state in global slices (large N), see LinearTftArgs
+    int lds_n;               // ragged k_optimf_refine: the n the launch's LDS is laid out for (>= every n of its range)
 };
 
-__global__ void __launch_bounds__(64, 2) k_optimf_linear_rows(const OptimFStageArgs sa) {
+template <bool RAGGED>
+__device__ __forceinline__ void optimf_linear_rows(const OptimFStageArgs& sa) {
     TFF_DYNAMIC_LDS(double, smem);
     const LinearTftArgs& a = sa.la;
+    if (RAGGED && a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call, as linear_f_pose_rows)
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
-        const int N = opaque_int(a.N);
-        const RowJob j = rows_begin(a, w, blk, N);
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(a, blk) < a.rrange[1] : blk * ROW_TRIPLETS < a.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
+        const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         int status = ST_OK;
-        if (N < 8) {                                                         // optimF.m:36-38 (wave-uniform: N is the batch's)
+        if (N < 8) {                                                         // optimF.m:36-38 (wave-uniform: N is the batch's, or the slot's)
             status = ST_TOO_FEW;
         } else {
             {
@@ -57,9 +67,15 @@ __global__ void __launch_bounds__(64, 2) k_optimf_linear_rows(const OptimFStageA
                 if (p < 9) r[18 + p] = w->nrm[p];
             }
         }
-        if (p == 0 && j.valid) { a.status[j.b] = status; if (a.iter) a.iter[j.b] = 0; }
+        if (p == 0 && j.valid) {
+            a.status[j.b] = status;
+            if (a.iter) a.iter[j.b] = 0;
+            if (RAGGED && status == ST_RETRY && a.retry_list) a.retry_list[atomicAdd(a.retry_count, 1)] = (int)j.b;
+        }
     }
 }
+__global__ void __launch_bounds__(64, 2) k_optimf_linear_rows(const OptimFStageArgs sa) { optimf_linear_rows<false>(sa); }
+__global__ void __launch_bounds__(64, 2) k_optimf_linear_rows_ragged(const OptimFStageArgs sa) { optimf_linear_rows<true>(sa); }
 
 // k_optimf_refine keeps what the iteration touches in every pass in LDS: xi (4 N) and -- STAGE_X -- the NORMALISED observations (6 N, the
 // correspondences mapped once: every pass of the fused kernel re-read them from L2 and mapped them again, a dependent global load per trip that
@@ -74,7 +90,8 @@ __host__ __device__ inline size_t optimf_refine_lds_bytes(int N, bool stage_x) {
     return (size_t)(OPTIMF_REFINE_FIXED_DOUBLES + 4 * N + 2 + (stage_x ? 6 * N : 0)) * sizeof(double);
 }
 
-template <int WAVES_PER_SIMD, bool STAGE_X>
+// RAGGED: one wavefront per entry of rlist[rrange[0] .. rrange[1]) (padding entries skipped); n and the first correspondence from the offsets
+template <int WAVES_PER_SIMD, bool STAGE_X, bool RAGGED = false>
 __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_optimf_refine(const OptimFStageArgs sa) {
     TFF_DYNAMIC_LDS(double, smem);
     const LinearTftArgs& a = sa.la;
@@ -82,12 +99,15 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_optimf_refine(const Opti
     OptimFLds* og = reinterpret_cast<OptimFLds*>(smem + sizeof(OptimFRefineLds) / sizeof(double));
     double* var = smem + OPTIMF_REFINE_FIXED_DOUBLES;
     double* xn = var;                                                        // STAGE_X: 6 N
-    double* oxi = sa.spill ? sa.spill + blockIdx.x * sa.spill_stride : var + (STAGE_X ? 6 * a.N : 0);
+    double* oxi = sa.spill ? sa.spill + blockIdx.x * sa.spill_stride : var + (STAGE_X ? 6 * (RAGGED ? sa.lds_n : a.N) : 0);
     const int lane = lane_id();
-    for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const long first = RAGGED ? (long)a.rrange[0] : 0, last = RAGGED ? (long)a.rrange[1] : a.B;
+    for (long wi = first + blockIdx.x; wi < last; wi += gridDim.x) {
+        const long b = RAGGED ? (long)a.rlist[wi] : wi;
+        if (RAGGED && b < 0) continue;                                       // wave-uniform: a padding slot
         if (a.status[b] != ST_OK) continue;                                  // wave-uniform: too few points, or left to the exact kernel
-        const int N = opaque_int(a.N);
-        const double* src = a.corresp + b * 6 * (long)N;
+        const int N = RAGGED ? ragged_n(a.offsets, b) : opaque_int(a.N);
+        const double* src = a.corresp + (RAGGED ? 6 * a.offsets[b] : b * 6 * (long)N);
         wave_sync();
         double* r = sa.rec + b * OPTIMF_REC_DOUBLES;
         if (lane < 18) w->Fm[lane] = r[lane];
@@ -158,23 +178,25 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_optimf_refine(const Opti
         if (lane == 0) {
             if (a.iter) a.iter[b] = iters;
             a.status[b] = !fine ? ST_RETRY : ((gst != ST_OK) ? -gst : ST_OK);   // negative: reported after k_optimf_finish_rows has produced the outputs
+            if (RAGGED && !fine && a.retry_list) a.retry_list[atomicAdd(a.retry_count, 1)] = (int)b;
         }
     }
 }
 
-__global__ void __launch_bounds__(64, 2) k_optimf_finish_rows(const OptimFStageArgs sa) {
+template <bool RAGGED>
+__device__ __forceinline__ void optimf_finish_rows(const OptimFStageArgs& sa) {
     TFF_DYNAMIC_LDS(double, smem);
     LinearTftArgs la = sa.la;
     la.iter = nullptr; la.dbg = nullptr;
     const int p = lane_id() & 15, row = lane_id() >> 4;
     RowLds* w = reinterpret_cast<RowLds*>(smem) + row;
     RowRt* rt = reinterpret_cast<RowRt*>(w->ov);
-    for (long blk = blockIdx.x; blk * ROW_TRIPLETS < la.B; blk += gridDim.x) {
-        const int N = opaque_int(la.N);
-        RowJob j = rows_begin(la, w, blk, N);                                // (calibration -> w->calm)
+    for (long blk = blockIdx.x; RAGGED ? rows_ragged_slot(la, blk) < la.rrange[1] : blk * ROW_TRIPLETS < la.B; blk += gridDim.x) {
+        const int N = RAGGED ? rows_ragged_n(la, blk) : opaque_int(la.N);
+        RowJob j = RAGGED ? rows_begin_ragged(la, w, blk) : rows_begin(la, w, blk, N);   // (calibration -> w->calm)
         const int s0 = la.status[j.b];
         const bool dead = s0 > 0;                                            // ST_TOO_FEW: no outputs; ST_RETRY: the exact kernel's (it stores them all)
-        if (s0 == ST_TOO_FEW) rows_store_nan(la, j, N);
+        if (s0 == ST_TOO_FEW) rows_store_nan<RAGGED>(la, j, N);
         const double* r = sa.rec + j.b * OPTIMF_REC_DOUBLES;
         w->t[p] = dead ? (((p % 9) % 4 == 0) ? 1.0 : 0.0) : r[p];                  // (a dead row works on a harmless matrix and stores nothing)
         if (p < 2) w->t[16 + p] = dead ? ((p == 1) ? 1.0 : 0.0) : r[16 + p];
@@ -207,10 +229,15 @@ __global__ void __launch_bounds__(64, 2) k_optimf_finish_rows(const OptimFStageA
         const bool ok = !row_any(!nok);
         wave_sync();
         rows_recover_prepare(w, rt);
-        int status = rows_pose_tail<true>(la, w, rt, j, N, ok);
+        int status = rows_pose_tail<true, false, RAGGED>(la, w, rt, j, N, ok);
         if (s0 < 0 && status != ST_RETRY) status = -s0;                         // OptimFPoseEstimation: the Gauss-Helmert loop's NaN / rank break
-        if (p == 0 && j.valid) la.status[j.b] = status;
+        if (p == 0 && j.valid) {
+            la.status[j.b] = status;
+            if (RAGGED && status == ST_RETRY && la.retry_list) la.retry_list[atomicAdd(la.retry_count, 1)] = (int)j.b;
+        }
     }
 }
+__global__ void __launch_bounds__(64, 2) k_optimf_finish_rows(const OptimFStageArgs sa) { optimf_finish_rows<false>(sa); }
+__global__ void __launch_bounds__(64, 2) k_optimf_finish_rows_ragged(const OptimFStageArgs sa) { optimf_finish_rows<true>(sa); }
 
 }  // namespace tff

@@ -10,6 +10,11 @@
 // Routes: items with n < split go to the exact tiers (the fixed-N launcher's `N < exact_below || TFF_OPT_SOLVER = 1`), the others to the
 // fast tiers; both are contiguous ranges of the slot list because it is sorted by n: route[0 .. 1] = [0, mid), route[2 .. 3] = [mid, total).
 // Everything stays on the device: the counts are never read by the host, the kernels that consume the list stop at the end of their range.
+//
+// OptimFPoseEstimation (optimf_rows_kernel.h) has two additions.  Its refinement runs in up to three launch classes by n (observations staged in
+// LDS | xi in LDS | xi in global slices): with cut[0] <= cut[1] set the scan also writes the three ranges [mid, c0), [c0, c1), [c1, total) to
+// route[4 .. 9], c_i being the first slot of bucket cut[i].  And its exact tiers have no row kernel: with retry_count set the scatter marks every
+// item with n < split ST_RETRY and appends it to the retry list (where the call has one), which the one-triplet exact kernel walks at the end of the chain.
 #pragma once
 #include "tft_kernel.h"
 
@@ -33,7 +38,11 @@ struct RaggedPlanArgs {
     double* T;
     int* iter;
     int* status;
+    int cut[2];           // cut[1] > 0: the refinement classes of OptimF, split <= cut[0] <= cut[1]; route then has RAGGED_ROUTE_INTS entries
+    int* retry_list;      // retry_count non-null: items with n < split get status ST_RETRY and, where the call has a list, an entry of it
+    int* retry_count;
 };
+constexpr int RAGGED_ROUTE_INTS = 10;        // route: [0, mid) | [mid, total) | with cut: [mid, c0) | [c0, c1) | [c1, total)
 
 // the slot count the plan can need: every bucket adds at most three padding slots
 inline long ragged_slots(long B, int n_max) { const long k = (long)n_max + 1; return B + 3 * (B < k ? B : k); }
@@ -79,7 +88,11 @@ __global__ void __launch_bounds__(RAGGED_SCAN_THREADS) k_ragged_scan(const Ragge
     int s = part[t] - sum;                                        // exclusive prefix of this thread's buckets
     for (int k = lo; k < hi; ++k) {
         const int c = a.hist[k], padded = (c + 3) & ~3;
-        if (k == a.split) { a.route[1] = s; a.route[2] = s; }
+        if (k == a.split) { a.route[1] = s; a.route[2] = s; if (a.cut[1] > 0) a.route[4] = s; }
+        if (a.cut[1] > 0) {
+            if (k == a.cut[0]) { a.route[5] = s; a.route[6] = s; }
+            if (k == a.cut[1]) { a.route[7] = s; a.route[8] = s; }
+        }
         a.start[k] = s;
         for (int q = c; q < padded; ++q) a.list[s + q] = -1;       // padding slots
         s += padded;
@@ -90,6 +103,12 @@ __global__ void __launch_bounds__(RAGGED_SCAN_THREADS) k_ragged_scan(const Ragge
         a.route[3] = total;
         if (a.split > a.n_max) { a.route[1] = total; a.route[2] = total; }
         if (a.split <= 0) { a.route[1] = 0; a.route[2] = 0; }
+        if (a.cut[1] > 0) {                                       // (0 <= split <= cut[0] <= cut[1]: a cut of 0 is bucket 0, written above)
+            if (a.split > a.n_max) a.route[4] = total;
+            if (a.cut[0] > a.n_max) { a.route[5] = total; a.route[6] = total; }
+            if (a.cut[1] > a.n_max) { a.route[7] = total; a.route[8] = total; }
+            a.route[9] = total;
+        }
     }
 }
 
@@ -99,6 +118,10 @@ __global__ void __launch_bounds__(256) k_ragged_scatter(const RaggedPlanArgs a) 
     int n;
     if (!ragged_item(a, b, &n)) return;
     a.list[a.start[n] + atomicAdd(a.fill + n, 1)] = (int)b;
+    if (a.retry_count && n < a.split) {                           // the first write of this item's status: no staged kernel walks its slot
+        a.status[b] = ST_RETRY;
+        if (a.retry_list) a.retry_list[atomicAdd(a.retry_count, 1)] = (int)b;   // (no list from B = 2^28 on: the exact kernel scans the statuses)
+    }
 }
 
 }  // namespace tff

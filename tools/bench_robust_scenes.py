@@ -9,8 +9,12 @@ triplet; Herz-Jesu, 56 triplets), 4 px threshold, n_hyp hypotheses per triplet:
 
 The two are alternated in one process, each the median of `--reps` repetitions after a warm-up, timed with the host clock around work that ends in a
 synchronise.  One JSON line per dataset; the results of (a) and (b) are compared bit for bit on the way (`equal`).
+--refine NAME adds the refine step to both: `refine=NAME` in the one call (ONE ragged call of that method on every triplet's inliers) against
+`refine=NAME` in every call of the loop (a fixed-N call per triplet, after reading its inlier count on the host); the loop then runs over the triplets
+the batch call found a pose with inliers for, the refined outputs join the comparison, and `refine_seconds` is the difference to the same run without the step.
 
   timeout 900 python tools/bench_robust_scenes.py [--hyp 1000 10000] [--method tft|f] [--threshold 4] [--reps 7] [--datasets fountain herzjesu]
+                                                  [--refine OptimFPoseEstimation]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--datasets", nargs="+", default=["fountain", "herzjesu"])
+    ap.add_argument("--refine", default=None, help="a method with a ragged route (api.RAGGED_METHODS): adds the refine step to both sides")
     args = ap.parse_args()
     from tft_vs_fund_amd import api
     ctx = api.Context(0)
@@ -47,17 +52,28 @@ def main():
         views = [(s, d_all[off[s]:off[s + 1]], d_calms[s]) for s in range(S) if sizes[s] >= n]
         rec = {"tool": "bench_robust_scenes", "dataset": name, "method": method, "triplets": S, "matches": int(off[-1]), "looped_triplets": len(views),
                "threshold": args.threshold, "candidates": args.candidates, "lo_rounds": args.rounds, "reps": args.reps}
+        if args.refine:
+            rec["refine"] = args.refine
         for n_hyp in args.hyp:
-            def batch():
-                return ctx.robust_pose_scenes(method, d_all, d_off, d_calms, n_hyp, args.threshold, seed=args.seed, ns_max=ns_max, **kw)
+            looped = views
+            if args.refine:                                                   # (the one-scene call has nothing to refine on where there is no pose or no inlier)
+                first = ctx.robust_pose_scenes(method, d_all, d_off, d_calms, n_hyp, args.threshold, seed=args.seed, ns_max=ns_max, **kw)
+                st, inl = first["status"].cpu().numpy(), first["inliers"].cpu().numpy()
+                looped = [v for v in views if st[v[0]] == 0 and inl[v[0]] > 0]
 
-            def loop():
-                return [(s, ctx.robust_pose(method, sc, cm, n_hyp, args.threshold, seed=args.seed + s, **kw)) for s, sc, cm in views]
+            def batch(refine=args.refine):
+                return ctx.robust_pose_scenes(method, d_all, d_off, d_calms, n_hyp, args.threshold, seed=args.seed, ns_max=ns_max, refine=refine, **kw)
 
-            times = {"batch": [], "loop": []}
+            def loop(refine=args.refine):
+                return [(s, ctx.robust_pose(method, sc, cm, n_hyp, args.threshold, seed=args.seed + s, refine=refine, **kw)) for s, sc, cm in looped]
+
+            runs = [("batch", batch), ("loop", loop)]
+            if args.refine:
+                runs += [("batch_plain", lambda: batch(None)), ("loop_plain", lambda: loop(None))]
+            times = {what: [] for what, _ in runs}
             res = {}
             for rep in range(args.reps + 1):                                  # repetition 0 is the warm-up
-                for what, fn in (("batch", batch), ("loop", loop)):
+                for what, fn in runs:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     res[what] = fn()
@@ -69,13 +85,17 @@ def main():
             for s, o in res["loop"]:
                 equal = equal and int(o["status"]) == int(a["status"][s]) and int(o["inliers"]) == int(a["inliers"][s])
                 equal = equal and np.array_equal(o["mask"].cpu().numpy(), a["mask"][off[s]:off[s + 1]])
-                for k in ("R_t_2", "R_t_3", "T"):
+                for k in ("R_t_2", "R_t_3", "T") + (("R_t_2_refined", "R_t_3_refined", "T_refined") if args.refine else ()):
                     equal = equal and np.array_equal(np.ascontiguousarray(o[k].cpu().numpy()).view(np.int64), np.ascontiguousarray(a[k][s]).view(np.int64))
             ta, tb = float(np.median(times["batch"])), float(np.median(times["loop"]))
             rec["hyp_%d" % n_hyp] = {"scenes_call_seconds": ta, "loop_seconds": tb, "loop_over_scenes_call": tb / ta,
                                      "scenes_call_min_max": [float(min(times["batch"])), float(max(times["batch"]))],
                                      "loop_min_max": [float(min(times["loop"])), float(max(times["loop"]))],
                                      "poses": int((a["status"] == 0).sum()), "inliers_total": int(a["inliers"].sum()), "equal": bool(equal)}
+            if args.refine:
+                pa, pb = float(np.median(times["batch_plain"])), float(np.median(times["loop_plain"]))
+                rec["hyp_%d" % n_hyp].update(looped_triplets=len(looped), refine_seconds={"scenes_call": ta - pa, "loop": tb - pb},
+                                             refined_ok=int((a["status_refined"] == 0).sum()), iter_refined_total=int(a["iter_refined"].sum()))
         print(json.dumps(rec), flush=True)
 
 
