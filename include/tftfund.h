@@ -103,6 +103,10 @@ typedef struct tff_ctx tff_ctx;
 #define TFF_OPT_BA_CLASSES 12 /* tff_bundle_adjust_ragged_*: how the items are launched.  0 (default): by batch size -- up to 256 items (every item resident at once
                              * even at one wavefront per CU) one launch sized for TFF_BA_MAX_N, larger batches three launch classes by LDS need; 1 = one
                              * launch always; 2 = three classes always (A/B switch, tools/bench_ba_ragged.py).  Identical results */
+#define TFF_OPT_SCORE 13    /* what tff_inlier_count_batch_dev / tff_inlier_count_scenes_dev write and tff_robust_pose_* rank by: 0 (default) the inlier
+                             * count; 1 the MSAC score, an int32 sum of per-inlier weights in [1, TFF_SCORE_UNITS] (formula at tff_inlier_count_batch_dev).
+                             * Any other value: TFF_E_INVALID.  Masks, their row sums, the refit batches and info[0] stay hard counts under either value */
+#define TFF_SCORE_UNITS 64  /* the MSAC weight of a perfect inlier: count <= score <= TFF_SCORE_UNITS * count */
 #define TFF_OPT_DEBUG_FP_HANDOVER 8 /* test hook: 1 = FaugPapa's block kernel hands every third triplet back to the generic workgroup kernel, as it does when its
                              * pseudo-inverse reports a failure (exercises that production fall-back; results must not depend on it beyond the
                              * generic kernel's LAPACK-level noise) */
@@ -241,7 +245,13 @@ int tff_repr_error_batch_dev(tff_ctx* ctx, const double* cams, int64_t cam_strid
 
 /* Inlier count of pose hypotheses against ONE shared scene (6 x Ns): cameras K1[I|0], K2 Rt2[b], K3 Rt3[b];
  * a correspondence is an inlier when all six reprojection residuals after triangulation are <= threshold in
- * absolute value (experiments_real.m:94-98).  counts B int32; err (B, RMS) optional. */
+ * absolute value (experiments_real.m:94-98).  counts B int32; err (B, RMS) optional.
+ * TFF_OPT_SCORE = 1 (MSAC): counts[b] is the hypothesis's score instead, on every route of this call (with or without err): the sum over its
+ * inliers -- the same rule decides who is one -- of the weight
+ *     w = 1 + (int)(63.0 * fmax(0.0, 1.0 - ss * c)),   c = 1 / (6 threshold^2) computed once by the host in double,
+ *     ss = (dx_0^2 + dy_0^2) + (dx_1^2 + dy_1^2) + (dx_2^2 + dy_2^2) of the six residuals the rule compares, added in that order,
+ * each dx^2 + dy^2 evaluated as fma(dx, dx, dy * dy) and 1 - ss * c as fma(-ss, c, 1.0), so that every route gives the same integer.  An outlier
+ * weighs 0, an inlier at the rim of the threshold box 1, a perfect one TFF_SCORE_UNITS: count <= score <= 64 * count <= 2^30 (Ns <= 2^24). */
 int tff_inlier_count_batch_dev(tff_ctx* ctx, const double* scene, int32_t Ns, const double* calm, const double* Rt2,
                                const double* Rt3, int64_t B, double threshold, int32_t* counts, double* err);
 
@@ -350,7 +360,8 @@ int tff_linear_f_pose_sampled_dev(tff_ctx* ctx, const double* scene, int32_t Ns,
 int tff_sample_indices_dev(tff_ctx* ctx, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, int32_t* sample_idx);
 
 /* Per-correspondence inlier flags of B pose hypotheses against the scene: mask (B x Ns, 0 / 1), counts (B, or NULL) = its row sums.  The rule and the
- * arithmetic per correspondence are those of tff_inlier_count_batch_dev (one shared device function), so the row sums equal that function's counts. */
+ * arithmetic per correspondence are those of tff_inlier_count_batch_dev (one shared device function), so the row sums equal that function's counts
+ * (its counts at TFF_OPT_SCORE = 0: this call writes flags and hard row sums under either value of that option). */
 int tff_inlier_mask_batch_dev(tff_ctx* ctx, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3,
                               int64_t B, double threshold, uint8_t* mask, int32_t* counts);
 
@@ -365,6 +376,12 @@ int tff_inlier_mask_batch_dev(tff_ctx* ctx, const double* scene, int32_t Ns, con
  *   4. the winner: the largest count, ties to the earlier candidate.  Rt2, Rt3 (12 each), T (27), mask (Ns flags of that pose; their sum is info[0]),
  *      info = [inlier count, index of the hypothesis the winner started from, refits it adopted, number of candidates], status = TFF_ST_OK.
  *      No successful hypothesis: status TFF_ST_NO_POSE, NaN in the three arrays, zero mask, info = [0, -1, 0, 0].
+ * TFF_OPT_SCORE = 1 (MSAC): "count" in steps 1 - 4 is the score tff_inlier_count_batch_dev writes under that option (w summed over the inliers, formula
+ *   there): 1. score[h] per hypothesis (a failed hypothesis still -1, the selection keys (score + 1) << 32 | ... unchanged); 2. the order is (score
+ *   descending, index ascending); 3. the masks, the packed refit batch and its offsets come from the hard rule as before, the refits are scored, and a
+ *   candidate adopts its refit iff the refit's status is 0 and its score is >= the candidate's: a refit of equal support that fits its inliers worse is
+ *   refused; 4. the winner has the largest score.  mask and info[0] are unchanged in meaning: the flags of the returned pose and their number.  The score
+ *   of the returned pose is one tff_inlier_count_batch_dev call away and is not part of info.
  * The result is a function of the arguments (seed included) and the context's options only.  Hypotheses are processed in chunks of 262 144 (their pose records,
  * 107 MB, the counts of all n_hyp hypotheses and K * Ns * 49 bytes for the refits are workspaces of the context); the result does not depend on the chunk size.
  * _dev: device pointers, no host synchronisation and no device-to-host copy (selection, compaction and offsets are kernels).  _host: host pointers, one
@@ -403,7 +420,7 @@ int tff_robust_pose_scenes_host(tff_ctx* ctx, int32_t method, const double* scen
                                 int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
                                 double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status);
 /* Inlier counts of S * per_scene pose hypotheses, hypothesis b against scene b / per_scene with that scene's CalM: counts[b] is what
- * tff_inlier_count_batch_dev returns for that pose against that scene alone (the same rule per correspondence).  The hypotheses of a scene whose offsets are
+ * tff_inlier_count_batch_dev returns for that pose against that scene alone (the same rule per correspondence; the same scores at TFF_OPT_SCORE = 1).  The hypotheses of a scene whose offsets are
  * negative, decreasing or above n_total count -1.  Four hypotheses per wavefront; a workgroup serves one scene at a time, staged in LDS when it fits 48 KB. */
 int tff_inlier_count_scenes_dev(tff_ctx* ctx, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int64_t S, const double* calm,
                                 int64_t calm_stride, const double* Rt2, const double* Rt3, int64_t per_scene, double threshold, int32_t* counts);

@@ -41,6 +41,9 @@ TFF_OPT_DEBUG_ADAPTIVE = 9
 TFF_OPT_PRE = 10
 TFF_OPT_COUNT_ROWS = 11
 TFF_OPT_BA_CLASSES = 12
+TFF_OPT_SCORE = 13
+SCORE_UNITS = 64             # TFF_SCORE_UNITS: the MSAC weight of a perfect inlier (count <= score <= SCORE_UNITS * count)
+SCORES = {"count": 0, "msac": 1}
 DEBUG_STRIDE = 128
 
 ST_OK, ST_TOO_FEW, ST_NONFINITE, ST_NO_POSE, ST_RANK, ST_NO_PARAM = 0, 1, 2, 3, 4, 5
@@ -311,6 +314,16 @@ class Context:
         """TFF_OPT_COUNT_ROWS: inlier counts with four hypotheses per wavefront (default) or one."""
         _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_COUNT_ROWS, int(bool(on))), "set_option")
 
+    def set_score(self, score):
+        """TFF_OPT_SCORE: "count" (default) = inlier_count / inlier_count_scenes return inlier counts and robust_pose / robust_pose_scenes rank their
+        hypotheses, adopt refits and pick the winner by them; "msac" = by the MSAC score instead, an int32 sum of per-inlier weights
+        1 + int(63 max(0, 1 - ss / (6 threshold^2))), ss the sum of the inlier's six squared residuals (include/tftfund.h).  inlier_mask, the returned
+        mask and `inliers` stay hard counts; with "msac" the robust estimators add out["score"], the score of the returned pose (-1: no pose)."""
+        if score not in SCORES:
+            raise ValueError("score must be one of %s, not %r" % (", ".join(map(repr, SCORES)), score))
+        _check(self.lib, self.lib.tff_ctx_set_option(self.handle, TFF_OPT_SCORE, SCORES[score]), "set_option")
+        self._score = SCORES[score]
+
     def set_ba_classes(self, mode):
         """TFF_OPT_BA_CLASSES: how bundle_adjust_ragged launches its items.  "auto" / 0 (default) = one launch sized for BA_MAX_N up to 256 items, three
         launch classes by LDS need beyond; 1 = one launch always; 2 = three classes always (A/B switch).  Identical results."""
@@ -560,7 +573,7 @@ class Context:
         return err
 
     def inlier_count(self, scene, calm, R_t_2, R_t_3, threshold=1.0, with_error=False):
-        """Inlier counts (experiments_real.m:94-98 rule) of B pose hypotheses against one scene (Ns, 6)."""
+        """Inlier counts (experiments_real.m:94-98 rule) of B pose hypotheses against one scene (Ns, 6); their MSAC scores after set_score("msac")."""
         self._begin()
         scene = self._t(scene); Ns = scene.shape[0]
         calm = self._t(calm).t().contiguous().reshape(27)
@@ -796,7 +809,9 @@ class Context:
         -> CUDA tensors (0-d for the five scalars) and no synchronisation; numpy in -> numpy / ints (the _host form).  refine = a name in POSE_METHODS:
         that method once on the final inliers through pose_batch (reads the count on the host), as R_t_2_refined, R_t_3_refined, T_refined,
         iter_refined, status_refined.  polish=True: BundleAdjustment on the pose and its inliers in one more call (bundle_adjust_ragged with the mask and the
-        offsets [0, Ns], built on the device; no synchronisation and no copy on the device path), as R_t_2_polished, R_t_3_polished, iter_polished, repr_err_polished, status_polished."""
+        offsets [0, Ns], built on the device; no synchronisation and no copy on the device path), as R_t_2_polished, R_t_3_polished, iter_polished, repr_err_polished, status_polished.
+        After set_score("msac") the hypotheses are ranked, refits adopted and the winner picked by the MSAC score, and `score` joins the dict: that of the
+        returned pose, from one more inlier_count call (0-d CUDA tensor, no synchronisation / int; -1 without a pose).  mask and inliers stay the hard rule."""
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
@@ -817,6 +832,8 @@ class Context:
                                                            ptr(info), ptr(st)), "tff_robust_pose_host")
             out = dict(R_t_2=Rt2.reshape(4, 3).T, R_t_3=Rt3.reshape(4, 3).T, T=T.reshape(3, 3, 3).transpose(2, 1, 0), mask=mask,
                        inliers=int(info[0]), hypothesis=int(info[1]), refits=int(info[2]), candidates=int(info[3]), status=int(st[0]))
+            if getattr(self, "_score", 0):
+                out["score"] = int(self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]) if out["status"] == 0 else -1
             inl = sc[mask != 0]
         else:
             if not (scene.is_cuda and scene.dtype == torch.float64 and scene.is_contiguous() and scene.dim() == 2 and scene.shape[1] == 6):
@@ -838,6 +855,9 @@ class Context:
                                                           self._p(T), self._p(mask), self._p(info), self._p(st)), "tff_robust_pose_dev")
             out = dict(R_t_2=Rt2.reshape(4, 3).t(), R_t_3=Rt3.reshape(4, 3).t(), T=T.reshape(3, 3, 3).permute(2, 1, 0), mask=mask,
                        inliers=info[0], hypothesis=info[1], refits=info[2], candidates=info[3], status=st[0])
+            if getattr(self, "_score", 0):                                   # one more count call on the returned pose; no pose (NaN): -1
+                sco = self.inlier_count(scene, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]
+                out["score"] = torch.where(st[0] == 0, sco, torch.full_like(sco, -1))
             inl = scene[mask != 0].contiguous() if refine is not None else None   # (boolean indexing reads the count on the host)
         if refine is not None:
             r = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
@@ -878,7 +898,8 @@ class Context:
         refine = a name in RAGGED_METHODS: that method on every scene's inliers in ONE pose_batch_ragged call (reconst=False), as R_t_2_refined, R_t_3_refined
         (S,3,4), T_refined (S,3,3,3), iter_refined, status_refined (S,): bit for bit what robust_pose(..., refine=...) gives for the scene alone; a scene
         without a pose has no inliers and gets ST_TOO_FEW and NaN.  On the device path the inliers are packed without reading a count (no
-        synchronisation when ns_max is passed).  The polish keeps starting from the robust poses."""
+        synchronisation when ns_max is passed).  The polish keeps starting from the robust poses.
+        After set_score("msac"): as robust_pose, with `score` (S,) from one more inlier_count_scenes call, -1 for a scene without a pose."""
         if refine is not None and refine not in RAGGED_METHODS:
             raise ValueError("robust_pose_scenes refines with one of %s, not %r" % (", ".join(RAGGED_METHODS), refine))
         if method not in ROBUST_METHODS:
@@ -906,6 +927,9 @@ class Context:
             out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
                        T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
                        candidates=info[:, 3], status=st)
+            if getattr(self, "_score", 0):
+                sco = self.inlier_count_scenes(sc, offsets, calm, out["R_t_2"], out["R_t_3"], threshold).cpu().numpy() if S else np.zeros(0, dtype=np.int32)
+                out["score"] = np.where(st == 0, sco, -1).astype(np.int32)
             if refine is not None:
                 keep = mask != 0
                 inl = np.ascontiguousarray(sc[keep])
@@ -935,6 +959,9 @@ class Context:
                                                              self._p(st)), "tff_robust_pose_scenes_dev")
         out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
                    mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        if getattr(self, "_score", 0):                                       # one more count call on the returned poses; no pose (NaN): -1
+            sco = self.inlier_count_scenes(scenes, offsets, calm, out["R_t_2"], out["R_t_3"], threshold) if S else torch.zeros_like(st)
+            out["score"] = torch.where(st == 0, sco, torch.full_like(sco, -1))
         if refine is not None:
             # every scene's inliers first, in scene order, without reading a count: a stable sort of 1 - mask; all Ntot rows are kept, the offsets say
             # where the inliers end (boolean indexing and nonzero would synchronise)

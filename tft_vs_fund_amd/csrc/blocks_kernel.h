@@ -64,7 +64,8 @@ struct ReprErrorArgs {
     int N;
     double thr;              // inlier threshold in pixels (per coordinate)
     double* err;             // B or null: RMS reprojection error (ReprError.m:65)
-    int* inliers;            // B or null: #{n : all six |residuals| <= thr}   (experiments_real.m:98)
+    int* inliers;            // B or null: #{n : all six |residuals| <= thr}   (experiments_real.m:98); the *_msac kernels: the sum of inlier_weight
+    double score_c;          // the *_msac kernels only: 1 / (6 thr^2), computed by the host in double (value-initialised, 0, for the count kernels)
 };
 // true only if S - Z (lower triangles) is positive definite with a margin that covers the approximate reciprocals (v_rcp_f64,
 // ~1e-7 relative) of this division-free pivot test: every pivot of the LDL' factorisation above 1e-4 of its diagonal entry
@@ -104,10 +105,28 @@ __device__ __forceinline__ void inlier_threshold_form(const double (&P)[3][12], 
 #pragma unroll
         for (int j = 0; j <= i; ++j) Zt[i][j] = k2 * (P[0][8 + i] * P[0][8 + j] + P[1][8 + i] * P[1][8 + j] + P[2][8 + i] * P[2][8 + j]);
 }
-// the whole rule, counts only: certain-outlier pivot test, then the certified DLT ladder, then the six comparisons; cnt += 1 for an inlier.  P: the
-// three cameras in registers, cam0 .. cam2: the same cameras in LDS (row-major 3 x 4), Zt: inlier_threshold_form(P, thr)
-__device__ __forceinline__ void count_if_inlier(const double (&P)[3][12], const double (&Zt)[4][4], const double* cam0, const double* cam1,
-                                                const double* cam2, const Pt6& p, const double thr, int& cnt) {
+// The MSAC weight of a correspondence that passes the rule (TFF_OPT_SCORE = 1): a truncated quadratic cost turned into an integer, so that a
+// hypothesis's score is a sum of int32 and keeps every bitwise contract the counts have.  ss = (dx_0^2 + dy_0^2) + (dx_1^2 + dy_1^2) + (dx_2^2 + dy_2^2)
+// of the six residuals the rule compares, each pair formed as fma(d_x, d_x, d_y d_y); c = 1 / (6 thr^2) comes from the host (no kernel divides).
+// w = 1 + (int)(63 max(0, 1 - ss c)), 1 - ss c formed as fma(-ss, c, 1): SCORE_UNITS for a perfect inlier, 1 at the rim of the box (ss <= 6 thr^2
+// there, so the max only guards rounding), 0 for an outlier -- count <= score <= SCORE_UNITS count.  The fused forms are spelled out and further
+// contraction is switched off in these two functions, so that no route's surrounding code can change the roundings: every route gives the same integer.
+constexpr int SCORE_UNITS = 64;              // TFF_SCORE_UNITS
+// ss + (dx^2 + dy^2): one product, one fma, one sum
+__device__ __forceinline__ double inlier_sq_add(const double ss, const double dx, const double dy) {
+#pragma clang fp contract(off)
+    return ss + fma(dx, dx, dy * dy);
+}
+__device__ __forceinline__ int inlier_weight(const double ss, const double c) {
+#pragma clang fp contract(off)
+    return 1 + (int)((double)(SCORE_UNITS - 1) * fmax(0.0, fma(-ss, c, 1.0)));
+}
+// the whole rule, counts only: certain-outlier pivot test, then the certified DLT ladder, then the six comparisons; cnt += 1 for an inlier
+// (MSAC = false), or += inlier_weight (MSAC = true: a compile-time variant, the count form keeps the instructions it had).  P: the
+// three cameras in registers, cam0 .. cam2: the same cameras in LDS (row-major 3 x 4), Zt: inlier_threshold_form(P, thr); c: see inlier_weight
+template <bool MSAC>
+__device__ __forceinline__ void score_if_inlier(const double (&P)[3][12], const double (&Zt)[4][4], const double* cam0, const double* cam1,
+                                                const double* cam2, const Pt6& p, const double thr, const double c, int& cnt) {
     double S[4][4], X[4];
     tri_zero(S);
     tri_accum(S, P[0], p.v[0], p.v[1]);
@@ -116,6 +135,7 @@ __device__ __forceinline__ void count_if_inlier(const double (&P)[3][12], const 
     if (certainly_positive_definite(S, Zt)) return;
     dlt_point_solve<true, true>(S, cam0, cam1, cam2, true, p.v[0], p.v[1], p.v[2], p.v[3], p.v[4], p.v[5], X);
     bool in = true;
+    double ss = 0.0;
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
         const double u = P[v][0] * X[0] + P[v][1] * X[1] + P[v][2] * X[2] + P[v][3] * X[3];
@@ -123,10 +143,19 @@ __device__ __forceinline__ void count_if_inlier(const double (&P)[3][12], const 
         const double z = P[v][8] * X[0] + P[v][9] * X[1] + P[v][10] * X[2] + P[v][11] * X[3];
         const double dx = u / z - p.v[2 * v], dy = w2 / z - p.v[2 * v + 1];
         in = in && (fabs(dx) <= thr) && (fabs(dy) <= thr);                  // sum(abs(residuals) > th, 1) == 0
+        if constexpr (MSAC) ss = inlier_sq_add(ss, dx, dy);
     }
-    cnt += in ? 1 : 0;
+    if constexpr (MSAC) cnt += in ? inlier_weight(ss, c) : 0;
+    else cnt += in ? 1 : 0;
 }
-__global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
+__device__ __forceinline__ void count_if_inlier(const double (&P)[3][12], const double (&Zt)[4][4], const double* cam0, const double* cam1,
+                                                const double* cam2, const Pt6& p, const double thr, int& cnt) {
+    score_if_inlier<false>(P, Zt, cam0, cam1, cam2, p, thr, 0.0, cnt);
+}
+// (a kernel template, not a shared device body under two kernels: with MSAC = false each of the three kernels below compiles to the instructions
+// it had as a plain kernel, and the names the launchers, the emulator sources and the profiles know stay: k_x = k_x_t<false>, k_x_msac = k_x_t<true>)
+template <bool MSAC>
+__global__ void __launch_bounds__(64, 4) k_repr_error_t(const ReprErrorArgs a) {
     __shared__ double cam[3][12];
     const int lane = lane_id();
     for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
@@ -176,6 +205,7 @@ __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
                 dlt_point_solve<true, true>(S, cam[0], cam[1], cam[2], true, p.v[0], p.v[1], p.v[2], p.v[3], p.v[4], p.v[5], X);
             }
             bool in = true;
+            double sw = 0.0;                                                 // (MSAC) this correspondence's squared residuals; ss runs over the scene
 #pragma unroll
             for (int v = 0; v < 3; ++v) {
                 const double u = P[v][0] * X[0] + P[v][1] * X[1] + P[v][2] * X[2] + P[v][3] * X[3];
@@ -184,8 +214,10 @@ __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
                 const double dx = u / z - p.v[2 * v], dy = w2 / z - p.v[2 * v + 1];
                 ss += dx * dx + dy * dy;
                 in = in && (fabs(dx) <= a.thr) && (fabs(dy) <= a.thr);     // sum(abs(residuals) > th, 1) == 0
+                if constexpr (MSAC) sw = inlier_sq_add(sw, dx, dy);
             }
-            cnt += in ? 1 : 0;
+            if constexpr (MSAC) cnt += in ? inlier_weight(sw, a.score_c) : 0;
+            else cnt += in ? 1 : 0;
         }
         ss = wave_sum(ss);
         cnt = wave_sum_i(cnt);
@@ -195,6 +227,8 @@ __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
         }
     }
 }
+constexpr auto k_repr_error = k_repr_error_t<false>;
+constexpr auto k_repr_error_msac = k_repr_error_t<true>;   // scores in `inliers` (TFF_OPT_SCORE = 1), with or without `err`
 
 // The int32 inlier counts of many hypotheses against ONE shared scene (config 4: experiments_real.m:94-98's rule per hypothesis) with the scene
 // staged in LDS once per workgroup: k_repr_error re-reads the scene through L1 / L2 for every hypothesis (a million hypotheses x 19 KB = 3.8 TB/s
@@ -202,7 +236,8 @@ __global__ void __launch_bounds__(64, 4) k_repr_error(const ReprErrorArgs a) {
 // hypotheses with a grid stride; same arithmetic per correspondence as k_repr_error's count-only path (certain-outlier pivot test, then the
 // certified DLT ladder for the correspondences that could be inliers), so the counts are identical.
 constexpr int INLIER_WG_WAVES = 4;
-__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 4) k_inlier_count_staged(const ReprErrorArgs a) {
+template <bool MSAC>
+__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 4) k_inlier_count_staged_t(const ReprErrorArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     double* scene = smem;                                                    // 6 N doubles
     double* camw = smem + 6 * (size_t)a.N + 36 * wave_in_block();            // the wavefront's three cameras (row-major 3 x 4)
@@ -235,19 +270,22 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 4) k_inlier_count_staged
         int cnt = 0;
 #pragma unroll 1
         for (int i = lane; i < a.N; i += WAVE) {
-            count_if_inlier(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, cnt);
+            score_if_inlier<MSAC>(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, a.score_c, cnt);
         }
         cnt = wave_sum_i(cnt);
         if (lane == 0) a.inliers[b] = cnt;
     }
 }
+constexpr auto k_inlier_count_staged = k_inlier_count_staged_t<false>;
+constexpr auto k_inlier_count_staged_msac = k_inlier_count_staged_t<true>;
 
 // The same counts with FOUR hypotheses per wavefront, one per row of 16 lanes (round 5): a wavefront per hypothesis spends a fifth of its instructions on
 // work that is the same for all its lanes -- composing three cameras on three lanes, pinning 36 camera entries and the ten entries of Z to scalar
 // registers -- and its seventh trip over a 400-correspondence scene runs 16 lanes of 64.  Here a row composes its hypothesis's cameras once into its own
 // 36 doubles of LDS, every position keeps them in vector registers, and 25 trips of 16 cover the scene exactly.  Per correspondence the same expressions
 // as above (certain-outlier pivot test, then the certified DLT ladder): identical counts (tests/test_gpu_blocks.py).
-__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_rows(const ReprErrorArgs a) {
+template <bool MSAC>
+__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_rows_t(const ReprErrorArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     double* scene = smem;                                                    // 6 N doubles
     const int lane = lane_id(), p = lane & 15, row = lane >> 4;
@@ -283,12 +321,14 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_rows(c
         int cnt = 0;
 #pragma unroll 1
         for (int i = p; i < a.N; i += 16) {
-            count_if_inlier(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, cnt);
+            score_if_inlier<MSAC>(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, a.score_c, cnt);
         }
-        const double tot = row_sum16((double)cnt);
+        const double tot = row_sum16((double)cnt);                           // (a score is at most 2^30: exact in a double)
         if (p == 0 && valid) a.inliers[b] = (int)tot;
     }
 }
+constexpr auto k_inlier_count_rows = k_inlier_count_rows_t<false>;
+constexpr auto k_inlier_count_rows_msac = k_inlier_count_rows_t<true>;
 
 // ---- transform_TFT ----------------------------------------------------------------------------
 struct TransformArgs {

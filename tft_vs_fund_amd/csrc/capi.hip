@@ -85,6 +85,7 @@ struct tff_ctx {
     int dbg_fp_handover = 0;               // TFF_OPT_DEBUG_FP_HANDOVER
     int dbg_adaptive = 0;                  // TFF_OPT_DEBUG_ADAPTIVE
     int count_rows = 1;                    // TFF_OPT_COUNT_ROWS: inlier counts four hypotheses per wavefront (default) or one
+    int score = 0;                         // TFF_OPT_SCORE: what tff_inlier_count_* write and the robust estimators rank by, 0 the inlier count, 1 the MSAC score (blocks_kernel.h::inlier_weight)
     int ba_classes = 0;                    // TFF_OPT_BA_CLASSES: ragged bundle adjustment, 0 the plan by batch size (launch_ba_ragged), 1 one launch class, 2 three
 };
 
@@ -755,23 +756,27 @@ int launch_ragged_optim_f(tff_ctx* c, const PoseCall& p) {
 }
 
 // ---- inlier counts and flags of pose hypotheses against one shared scene ------------------------------------------------------------------------
+// the c of blocks_kernel.h::inlier_weight: 1 / (6 thr^2) in double, once per call, so that no kernel divides
+double score_scale(double threshold) { return 1.0 / (6.0 * threshold * threshold); }
 int launch_inlier_count(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B, double threshold,
                         int32_t* counts, double* err) {
     tff::ReprErrorArgs a{nullptr, 0, calm, Rt2, Rt3, scene, 0, nullptr, (long)B, Ns, threshold, err, counts};
+    const bool msac = c->score == 1;                                         // every route has its *_msac twin: the same launch, scores instead of counts
+    if (msac) a.score_c = score_scale(threshold);
     const size_t staged = ((size_t)6 * Ns + 36 * tff::INLIER_WG_WAVES) * sizeof(double);
-    if (err || staged > 48 * 1024 || B < 4096) return launch(c, tff::k_repr_error, tff::pose_grid(B), 64, 0, a);
+    if (err || staged > 48 * 1024 || B < 4096) return launch(c, msac ? tff::k_repr_error_msac : tff::k_repr_error, tff::pose_grid(B), 64, 0, a);
     // counts only, many hypotheses, a scene that fits the LDS a few times over: stage it once per workgroup (blocks_kernel.h)
     if (c->count_rows) {                                                 // four hypotheses per wavefront (blocks_kernel.h::k_inlier_count_rows): two workgroups per CU
         const size_t staged_rows = ((size_t)6 * Ns + 36 * 4 * tff::INLIER_WG_WAVES) * sizeof(double);
         long grid_rows = 256L * 2;
         const long per_wg = 4L * tff::INLIER_WG_WAVES;
         if (grid_rows * per_wg > B) grid_rows = (B + per_wg - 1) / per_wg;
-        return launch(c, tff::k_inlier_count_rows, (unsigned)grid_rows, 64 * tff::INLIER_WG_WAVES, staged_rows, a);
+        return launch(c, msac ? tff::k_inlier_count_rows_msac : tff::k_inlier_count_rows, (unsigned)grid_rows, 64 * tff::INLIER_WG_WAVES, staged_rows, a);
     }
     const int per_cu = (int)((LDS_LIMIT / (staged + 512) < 4) ? LDS_LIMIT / (staged + 512) : 4);
     long grid = 256L * per_cu;
     if (grid * tff::INLIER_WG_WAVES > B) grid = (B + tff::INLIER_WG_WAVES - 1) / tff::INLIER_WG_WAVES;
-    return launch(c, tff::k_inlier_count_staged, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, staged, a);
+    return launch(c, msac ? tff::k_inlier_count_staged_msac : tff::k_inlier_count_staged, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, staged, a);
 }
 // one wavefront per hypothesis (robust_kernel.h::k_inlier_mask); gate: see InlierMaskArgs
 int launch_inlier_mask(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B, double threshold,
@@ -914,7 +919,9 @@ int launch_count_scenes(tff_ctx* c, const tff::SceneSet& set, const double* Rt2,
     const long want = 6L * set.ns_max;
     const int stage = (int)(want < tff::SCENES_STAGE_MAX_DOUBLES ? want : tff::SCENES_STAGE_MAX_DOUBLES);
     tff::ScenesCountArgs a{set, Rt2, Rt3, (long)first, (long)B, (long)per, slab, threshold, counts, stage};
-    return launch(c, tff::k_inlier_count_scenes, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, ((size_t)36 * rows + (size_t)stage) * sizeof(double), a);
+    const bool msac = c->score == 1;
+    if (msac) a.score_c = score_scale(threshold);
+    return launch(c, msac ? tff::k_inlier_count_scenes_msac : tff::k_inlier_count_scenes, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, ((size_t)36 * rows + (size_t)stage) * sizeof(double), a);
 }
 // device pointers; the lock is held and the context's device current
 int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall& q) {
@@ -1006,8 +1013,13 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     }
     // 4. per scene the winner, and the flags of its pose in the scene's range of the packed mask (skipped where there is none)
     TFF_TRY(launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin));
-    return launch(c, tff::k_scenes_mask, tff::pose_grid(S), 64, 0,
-                  tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, nullptr, nullptr, q.status});
+    if (c->score != 1)
+        return launch(c, tff::k_scenes_mask, tff::pose_grid(S), 64, 0,
+                      tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, nullptr, nullptr, q.status});
+    // MSAC: info[0] holds the winner's score; the row sums of the returned flags replace it (mask_cnt is free again: C >= S ints)
+    TFF_TRY(launch(c, tff::k_scenes_mask, tff::pose_grid(S), 64, 0,
+                   tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, mask_cnt, nullptr, q.status}));
+    return launch(c, tff::k_scenes_info, (unsigned)((S + 255) / 256), 256, 0, tff::ScenesInfoArgs{mask_cnt, q.status, q.info, (long)S});
 }
 
 }  // namespace
@@ -1090,6 +1102,7 @@ int tff_ctx_set_option(tff_ctx* c, int option, long value) {
         case TFF_OPT_ROWS: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "rows must be 0, 1 or 2"); c->rows = (int)value; return 0;
         case TFF_OPT_PRE: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "pre must be 0, 1 or 2"); c->pre = (int)value; return 0;
         case TFF_OPT_COUNT_ROWS: c->count_rows = value != 0; return 0;
+        case TFF_OPT_SCORE: if (value != 0 && value != 1) return fail(TFF_E_INVALID, "score must be 0 (count) or 1 (MSAC)"); c->score = (int)value; return 0;
         case TFF_OPT_BA_CLASSES: if (value < 0 || value > 2) return fail(TFF_E_INVALID, "ba_classes must be 0, 1 or 2"); c->ba_classes = (int)value; return 0;
         case TFF_OPT_DEBUG_FP_HANDOVER: c->dbg_fp_handover = value != 0; return 0;
         case TFF_OPT_DEBUG_ADAPTIVE: c->dbg_adaptive = value != 0; return 0;

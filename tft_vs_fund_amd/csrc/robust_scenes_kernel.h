@@ -78,11 +78,13 @@ struct ScenesCountArgs {
     double thr;
     int* counts;             // B; -1 for a hypothesis of an invalid scene
     int stage_doubles;       // LDS doubles behind the cameras
+    double score_c;          // k_inlier_count_scenes_msac only: 1 / (6 thr^2) from the host (blocks_kernel.h::inlier_weight); 0 for the count kernel
 };
 constexpr int SCENES_COUNT_ROWS = 4 * INLIER_WG_WAVES;       // hypotheses a workgroup serves at a time
 constexpr int SCENES_STAGE_MIN = 8;                          // shorter segments read their scene through L2
 constexpr int SCENES_STAGE_MAX_DOUBLES = 48 * 1024 / 8 - 36 * SCENES_COUNT_ROWS;   // scene + cameras within the 48 KB of the one-scene launcher
 
+template <bool MSAC>
 __device__ __forceinline__ void scenes_count_segment(const ScenesCountArgs& a, const double* scene, const int n, const double* calm, double* camw,
                                                      const long seg_begin, const long seg_end) {
     const int p = lane_id() & 15, row = lane_id() >> 4;
@@ -111,13 +113,14 @@ __device__ __forceinline__ void scenes_count_segment(const ScenesCountArgs& a, c
         int cnt = 0;
 #pragma unroll 1
         for (int i = p; i < n; i += 16) {
-            count_if_inlier(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, cnt);
+            score_if_inlier<MSAC>(P, Zt, camw, camw + 12, camw + 24, load_pt(scene, i), a.thr, a.score_c, cnt);
         }
         const double tot = row_sum16((double)cnt);
         if (p == 0 && valid) a.counts[b] = (int)tot;
     }
 }
-__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_scenes(const ScenesCountArgs a) {
+template <bool MSAC>
+__global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_scenes_t(const ScenesCountArgs a) {
     TFF_DYNAMIC_LDS(double, smem);
     double* camw = smem + 36 * (4 * wave_in_block() + (lane_id() >> 4));     // the row's three cameras (row-major 3 x 4)
     double* staged = smem + 36 * SCENES_COUNT_ROWS;                          // up to stage_doubles of one scene
@@ -139,14 +142,16 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_scenes
                 double2* d2 = reinterpret_cast<double2*>(staged);
                 for (int i = thread_in_block(); i < 3 * n; i += 64 * INLIER_WG_WAVES) d2[i] = s2[i];
                 __syncthreads();
-                scenes_count_segment(a, staged, n, calm, camw, b, seg_end);
+                scenes_count_segment<MSAC>(a, staged, n, calm, camw, b, seg_end);
             } else {
-                scenes_count_segment(a, src, n, calm, camw, b, seg_end);
+                scenes_count_segment<MSAC>(a, src, n, calm, camw, b, seg_end);
             }
         }
         b = seg_end;
     }
 }
+constexpr auto k_inlier_count_scenes = k_inlier_count_scenes_t<false>;   // (the pattern of blocks_kernel.h::k_repr_error_t)
+constexpr auto k_inlier_count_scenes_msac = k_inlier_count_scenes_t<true>;
 
 // ---- per-correspondence inlier flags with a scene lookup ---------------------------------------------------------------------------------------
 struct ScenesMaskArgs {
@@ -304,6 +309,14 @@ __global__ void __launch_bounds__(64) k_scenes_finish(const ScenesFinishArgs f) 
         f.info[sc * 4 + 3] = ncand;
         f.status[sc] = st != ST_OK ? st : (win >= 0 ? ST_OK : ST_NO_POSE);
     }
+}
+
+// TFF_OPT_SCORE = 1 only: k_scenes_finish put the winner's SCORE into info[0]; the row sums of the final k_scenes_mask launch (the number of set flags of
+// each returned mask, written for the scenes with status 0) take its place, as the gated k_inlier_mask launch does for tff_robust_pose_*
+struct ScenesInfoArgs { const int* flags; const int* status; int* info; long S; };
+__global__ void __launch_bounds__(256) k_scenes_info(const ScenesInfoArgs a) {
+    const long sc = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (sc < a.S && a.status[sc] == 0) a.info[sc * 4] = a.flags[sc];
 }
 
 }  // namespace tff
