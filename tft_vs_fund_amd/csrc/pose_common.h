@@ -643,7 +643,7 @@ __device__ __forceinline__ void vote_one(const double (&SA)[6], const VoteCam& c
         const double dmin2 = fmin(d1 * d1, d2 * d2);
         const bool certain = Gp > 0.0 && dmin2 * Gp * Gp > rhs * rhs * zz;  // false for NaN / inf
         all_certain = all_certain && certain;
-        score += (int)sgn(d1) + (int)sgn(d2);
+        score += sgn_i(d1) + sgn_i(d2);
     }
     if constexpr (KEEP) {
 #pragma unroll

@@ -10,6 +10,7 @@ namespace tff {
 struct Mat3 { double m[3][3]; };
 
 __device__ __forceinline__ double sgn(double x) { return (x > 0.0) ? 1.0 : ((x < 0.0) ? -1.0 : 0.0); }   // MATLAB sign()
+__device__ __forceinline__ int sgn_i(double x) { return (int)(x > 0.0) - (int)(x < 0.0); }                 // (int)sgn(x) from the two compare masks: no double select, no conversion
 
 __device__ __forceinline__ Mat3 mat3_mul(const Mat3& a, const Mat3& b) {
     Mat3 c;

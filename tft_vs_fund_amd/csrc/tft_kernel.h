@@ -164,24 +164,51 @@ __device__ __forceinline__ void ctc_entry(int j, int jp, double& sign, int& idx)
     else if (a < 2) { sign = -1.0; idx = 1 + a; }
     else { sign = 1.0; idx = 3; }
 }
+// Row j of that table in one word: bits [2 q + 1 : 2 q] = q-index of entry (j, q), bits [8 + 2 q + 1 : 8 + 2 q] = its sign + 1.
+// Index and sign of a whole row then cost one shift and six bit-field extracts on a lane instead of three walks through ctc_entry.
+constexpr unsigned ctc_row_word(const int j) {
+    unsigned w = 0;
+    for (int q = 0; q < 3; ++q) {
+        const int a = (j < q) ? j : q, b = (j < q) ? q : j;
+        const int idx = (b < 2) ? 0 : ((a < 2) ? 1 + a : 3);
+        const int sg = (b < 2) ? ((a == b) ? 1 : 0) : ((a < 2) ? -1 : 1);
+        w |= (unsigned)idx << (2 * q) | (unsigned)(sg + 1) << (8 + 2 * q);
+    }
+    return w;
+}
+__device__ __forceinline__ void ctc_row(const int j, double (&sign)[3], int (&idx)[3]) {
+    constexpr unsigned long long ROWS = (unsigned long long)ctc_row_word(0) | (unsigned long long)ctc_row_word(1) << 16 | (unsigned long long)ctc_row_word(2) << 32;
+    const unsigned w = (unsigned)(ROWS >> (16 * j));
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        idx[q] = (int)((w >> (2 * q)) & 3u);
+        sign[q] = (double)((int)((w >> (8 + 2 * q)) & 3u) - 1);              // exactly the 1.0 / 0.0 / -1.0 of ctc_entry (0 -> +0.0)
+    }
+}
+// hht_index(i, 0..2) in one word: bits [3 ip + 2 : 3 ip]
+__device__ __forceinline__ unsigned hht_row_word(const int i) {
+    constexpr unsigned R0 = 0u | 1u << 3 | 2u << 6, R1 = 1u | 3u << 3 | 4u << 6, R2 = 2u | 4u << 3 | 5u << 6;
+    constexpr unsigned long long ROWS = (unsigned long long)R0 | (unsigned long long)R1 << 16 | (unsigned long long)R2 << 32;
+    return (unsigned)(ROWS >> (16 * i));
+}
 // Row r = (j,k,i) of G: entry (j',k',i') = s2(j,j') s3(k,k') mom[h(i,i')][i3(k,k')][i2(j,j')].
 __device__ __forceinline__ void gram_row27(const double* mom, int r, double (&g)[27], double& diag) {
     const int i = r / 9, k = (r % 9) / 3, j = r % 3;
     double s2[3], s3[3];
     int i2[3], i3[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { ctc_entry(j, q, s2[q], i2[q]); ctc_entry(k, q, s3[q], i3[q]); }
+    ctc_row(j, s2, i2);
+    ctc_row(k, s3, i3);
+    const unsigned hw = hht_row_word(i);
 #pragma unroll
     for (int ip = 0; ip < 3; ++ip) {
-        const double* M = mom + 16 * hht_index(i, ip);
+        const double* M = mom + 16 * (int)((hw >> (3 * ip)) & 7u);
 #pragma unroll
         for (int kp = 0; kp < 3; ++kp)
 #pragma unroll
             for (int jp = 0; jp < 3; ++jp) g[jp + 3 * kp + 9 * ip] = s2[jp] * s3[kp] * M[4 * i3[kp] + i2[jp]];
     }
-    diag = 0.0;
-#pragma unroll
-    for (int c = 0; c < 27; ++c) diag = (c == r) ? g[c] : diag;
+    // g[r] itself: s2(j,j) = s3(k,k) = 1.0 exactly, so the diagonal entry is the moment -- one read instead of a 27-way select
+    diag = mom[16 * (int)((hw >> (3 * i)) & 7u) + ((k == 2) ? 12 : 0) + ((j == 2) ? 3 : 0)];
 }
 
 // orthonormal frame [e | q | q'] of a unit vector e, row-major Q[3*r + c]
@@ -200,10 +227,32 @@ __device__ __forceinline__ void frame_of(const double* e, double* Q) {
 }
 
 // column a = (i, m) of Up: the 3-vectors (Q2 column jj, Q3 column kk), (jj,kk) = m<3 ? (0,m) : (m-2,0)
-__device__ __forceinline__ void up_factors(const double* Q, int m, double (&a2)[3], double (&a3)[3]) {
-    const int jj = (m < 3) ? 0 : m - 2, kk = (m < 3) ? m : 0;
+__device__ __forceinline__ void up_factors_jk(const double* Q, int jj, int kk, double (&a2)[3], double (&a3)[3]) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) { a2[q] = Q[3 * q + jj]; a3[q] = Q[9 + 3 * q + kk]; }
+}
+__device__ __forceinline__ void up_factors(const double* Q, int m, double (&a2)[3], double (&a3)[3]) {
+    up_factors_jk(Q, (m < 3) ? 0 : m - 2, (m < 3) ? m : 0, a2, a3);
+}
+// Everything the Gp build (Gp = Up' G Up, 15 x 15, packed lower triangle) needs to know about entry e = tri_index(a, b), in 16 bits:
+// (jj, kk) of up_factors for column a (bits 1:0, 3:2) and column b (5:4, 7:6), hht_index(a / 5, b / 5) (10:8).  The row kernels walk the
+// entries e = p + 16 t, t = 0 .. 7: position p's eight words are w[p][0] (t = 0 .. 3) and w[p][1] (t = 4 .. 7), 16 bits each from the bottom.
+struct GpIndexTable { unsigned long long w[16][2]; };
+constexpr GpIndexTable make_gp_index_table() {
+    GpIndexTable t{};
+    for (int p = 0; p < 16; ++p)
+        for (int k = 0; k < 8; ++k) {
+            const int e = p + 16 * k;
+            if (e >= 120) continue;
+            int a = 0;
+            while ((a + 1) * (a + 2) / 2 <= e) ++a;
+            const int b = e - a * (a + 1) / 2;
+            const int ma = a % 5, mb = b % 5, lo = b / 5, hi = a / 5;        // b <= a
+            const unsigned word = (unsigned)((ma < 3) ? 0 : ma - 2) | (unsigned)((ma < 3) ? ma : 0) << 2 | (unsigned)((mb < 3) ? 0 : mb - 2) << 4
+                                  | (unsigned)((mb < 3) ? mb : 0) << 6 | (unsigned)((lo == 0) ? hi : ((lo == 1) ? 2 + hi : 5)) << 8;
+            t.w[p][k >> 2] |= (unsigned long long)word << (16 * (k & 3));
+        }
+    return t;
 }
 
 // Row e (0..3) of correspondence (x1,y1,x2,y2,x3,y3) in the 4N x 27 system of linearTFT.m:51-62 is

@@ -88,8 +88,18 @@ __device__ __forceinline__ void rows_stamp(double* dbg, const int slot) {
 __device__ __forceinline__ void rows_centroids(const RowSrc& s, const int N, double (&c)[6]) {
     const int p = rows_p();
     double sm[6] = {0, 0, 0, 0, 0, 0};
+    int i0 = 0;
 #pragma unroll 1
-    for (int i0 = 0; i0 < N; i0 += 4 * ROWL) {                               // wave-uniform trip count; lanes past the end add zeros
+    for (; i0 + 4 * ROWL <= N; i0 += 4 * ROWL) {                             // whole groups of 64 (N is wave-uniform): no lane is past the end, nothing to mask
+        Pt6 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = rows_load(s, i0 + ROWL * u + p);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) sm[k] += q[u].v[k];
+    }
+    if (i0 < N) {                                                            // the tail group: lanes past the end add zeros (the same additions in the same order)
         Pt6 q[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) { const int i = i0 + ROWL * u + p; q[u] = rows_load(s, (i < N) ? i : 0); }
@@ -364,23 +374,24 @@ __device__ __forceinline__ bool rows_linear_tft_middle(RowLds* w, double* dbg, c
     ok = !row_any(!eok) && ok;
     rows_stamp(dbg, 5);
     if (dbg && p < 6) dbg[27 + p] = w->epi[p];
-    if (p == 0) frame_of(w->epi, w->Q);                                      // Q2 from e21
-    if (p == 1) frame_of(w->epi + 3, w->Q + 9);                              // Q3 from e31
+    if (p < 2) frame_of(w->epi + 3 * p, w->Q + 9 * p);                       // Q2 from e21 (position 0), Q3 from e31 (position 1): one pass for both
     wave_sync();
     // Gp = Up' G Up (15x15), lower triangle, packed into the overlay; entry (a,b), a = 5 i + m
     double* Gp = w->ov;
+    // (which columns of Q and which block of moments entry e takes come from a table, tft_kernel.h::GpIndexTable, instead of a square root,
+    // two search loops and four divisions per entry)
+    constexpr GpIndexTable gp_index = make_gp_index_table();
+    const unsigned long long gw0 = gp_index.w[rows_p()][0], gw1 = gp_index.w[rows_p()][1];
+    int trip = 0;
 #pragma unroll 1
-    for (int e = p; e < 120; e += ROWL) {
-        int a = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        while (tri_index(a + 1, 0) <= e) ++a;
-        while (tri_index(a, 0) > e) --a;
-        const int b = e - tri_index(a, 0);
+    for (int e = p; e < 120; e += ROWL, ++trip) {
+        const unsigned gw = (unsigned)(((trip < 4) ? gw0 : gw1) >> (16 * (trip & 3)));
         double a2[3], a3[3], b2[3], b3[3], c2[4], c3[4];
-        up_factors(w->Q, a % 5, a2, a3);
-        up_factors(w->Q, b % 5, b2, b3);
+        up_factors_jk(w->Q, (int)(gw & 3u), (int)((gw >> 2) & 3u), a2, a3);
+        up_factors_jk(w->Q, (int)((gw >> 4) & 3u), (int)((gw >> 6) & 3u), b2, b3);
         cvec(a2, b2, c2);
         cvec(a3, b3, c3);
-        Gp[e] = bilinear44(w->mom + 16 * hht_index(a / 5, b / 5), c3, c2);
+        Gp[e] = bilinear44(w->mom + 16 * (int)((gw >> 8) & 7u), c3, c2);
     }
     wave_sync();
     rows_stamp(dbg, 6);
@@ -657,7 +668,7 @@ __device__ __forceinline__ bool rows_votes(const RowSrc& s, const int N, const R
                         const double* pr = rt->candRt[0] + opaque_lane_int(offA[0]);
                         const double s4 = sgn(X[3]);                         // X1 = X ./ X(4)
                         const double d1 = X[2] * s4, d2 = (pr[8] * X[0] + pr[9] * X[1] + pr[10] * X[2] + pr[11] * X[3]) * s4;
-                        scA[0] += have ? (int)sgn(d1) + (int)sgn(d2) : 0;
+                        scA[0] += have ? sgn_i(d1) + sgn_i(d2) : 0;
                         certA[0] = certA[0] && (conv || !have);
                     }
                     const double iw = 1.0 / X[3];
