@@ -419,6 +419,36 @@ int tff_robust_pose_scenes_dev(tff_ctx* ctx, int32_t method, const double* scene
 int tff_robust_pose_scenes_host(tff_ctx* ctx, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                                 int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
                                 double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status);
+/* ---- the same with an early stop per scene: hypotheses in rounds, up to a cap, until a confidence is reached -------------------------------------------------
+ * Arguments beyond tff_robust_pose_scenes_*: confidence c, 0 < c < 1; first_round, a multiple of 4 and >= 4; n_hyp is now the CAP per scene; used (S int32).
+ *   Round ends: e_r = min(n_hyp, first_round << (r - 1)) for r = 1 .. R, until e_R = n_hyp; e_0 = 0.  At most 32 rounds.
+ *   Thresholds: one per round, computed by the host in double: qmin_r = -expm1(log1p(-c) / e_r).  (A sample of n_sample correspondences is all-inlier with
+ *   probability about w^n_sample at an inlier ratio w; e_r such samples all miss with probability (1 - w^n_sample)^e_r <= 1 - c iff w^n_sample >= qmin_r.)
+ *   Round r draws the hypotheses h in [e_(r-1), e_r) of every scene that is still live.  Hypothesis h of scene s is what it is in the fixed call: a function of
+ *   (seed + s, h).
+ *   The stop rule, after round r, for each live scene of n_s correspondences: best = the largest of the scene's counts so far, a failed hypothesis counting
+ *   -1.  I = best (TFF_OPT_SCORE = 0) or best / TFF_SCORE_UNITS in integer division (TFF_OPT_SCORE = 1: a lower bound on that hypothesis's inlier count, so
+ *   MSAC never stops earlier than the count would for the same hypothesis).  w = (double)I / (double)n_s; q = w multiplied by itself n_sample - 1 times, in
+ *   that order, in double.  The scene stops iff I >= 1 and q >= qmin_r.  No log and no pow runs on the device: given qmin_r from tff_robust_round_plan, the
+ *   same few lines of numpy reproduce every decision exactly.
+ *   used[s] = e_r for a scene that stops after round r, n_hyp for one that never stops, 0 for a scene that is TFF_ST_TOO_FEW or TFF_ST_BAD_OFFSETS (it never
+ *   runs).
+ *   After the rounds, steps 2 - 4 of tff_robust_pose_dev run unchanged on the scene-major counts (stride n_hyp): the whole array is -1 before round 1, so a
+ *   hypothesis that was never drawn is never selected.
+ * THE CONTRACT: the outputs of scene s are bit for bit those of tff_robust_pose_dev on that scene alone with n_hyp = used[s] and the seed seed + s, under the
+ * same context options.  S, the neighbouring scenes, the chunking of a round's S * (e_r - e_(r-1)) rows (262 144 per chunk) and first_round do not matter
+ * beyond what used[s] says.  first_round >= n_hyp is one round: the fixed call, with used = n_hyp for the valid scenes.
+ * What the early stop saves: the hypotheses of a scene that has stopped get sample indices -1, their inlier counts are skipped, and with n_sample below
+ * TFF_OPT_EXACT_BELOW (the default n_sample of 7 / 8 is) a wavefront of the pose kernel whose four hypotheses are all of that kind leaves at once -- whole
+ * wavefronts are, as first_round and the chunk size are multiples of 4, a last round of odd length apart.  With n_sample >= TFF_OPT_EXACT_BELOW the fast-tier
+ * pose kernels serve the call and are unchanged: there such a hypothesis still costs a pose (whose outputs are NaN / TFF_ST_TOO_FEW as before), and only
+ * the counting is saved.
+ * TFF_E_INVALID: what tff_robust_pose_scenes_* refuses; a confidence outside (0, 1) or NaN; first_round < 4 or not a multiple of 4; more than 32 rounds;
+ * a null `used`.  _dev: no host synchronisation and no device-to-host copy; every workspace is reserved before the first launch.  Workspaces beyond the fixed
+ * call's: 4 bytes per row of a chunk and 12 S bytes. */
+/* Declared in tftfund_adaptive.h, which this header includes at its end: tff_robust_pose_scenes_adaptive_dev / _host (the arguments of
+ * tff_robust_pose_scenes_*, plus `double confidence, int32_t first_round` after lo_rounds and `int32_t* used` before status) and tff_robust_round_plan. */
+
 /* Inlier counts of S * per_scene pose hypotheses, hypothesis b against scene b / per_scene with that scene's CalM: counts[b] is what
  * tff_inlier_count_batch_dev returns for that pose against that scene alone (the same rule per correspondence; the same scores at TFF_OPT_SCORE = 1).  The hypotheses of a scene whose offsets are
  * negative, decreasing or above n_total count -1.  Four hypotheses per wavefront; a workgroup serves one scene at a time, staged in LDS when it fits 48 KB. */
@@ -491,4 +521,5 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 #ifdef __cplusplus
 }
 #endif
+#include "tftfund_adaptive.h"   /* entry points added after library version 103 */
 #endif

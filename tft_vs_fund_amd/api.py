@@ -126,12 +126,17 @@ def load_library(path=None):
             "tff_robust_pose_scenes_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
             "tff_robust_pose_scenes_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, V, V, V, V, V, V],
             "tff_inlier_count_scenes_dev": [V, V, V, I64, I64, V, I64, V, V, I64, F64, V],
+            "tff_robust_pose_scenes_adaptive_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, V, V, V, V, V, V],
+            "tff_robust_pose_scenes_adaptive_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, V, V, V, V, V, V],
+            "tff_robust_round_plan": [F64, I64, I32, V, V, V],
             "tff_bundle_adjust_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_class_bounds": [V],
             "tff_optim_f_ragged_bounds": [V],
         }
         for name, sig in protos.items():
+            if path is not None and name in ADAPTIVE_SYMBOLS and not hasattr(lib, name):
+                continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
@@ -177,6 +182,9 @@ EXPORTED_SYMBOLS = [
     "tff_bundle_adjust_ragged_dev", "tff_bundle_adjust_ragged_host", "tff_bundle_adjust_ragged_class_bounds",
     "tff_optim_f_ragged_bounds",
 ]
+# ... and every symbol include/tftfund_adaptive.h declares: the entry points added after library version 103, in the header that tftfund.h includes at
+# its end.  (EXPORTED_SYMBOLS is the ABI of version 103 and is pinned as such: tests/test_score_cpu.py, tests/test_capi_symbols.py.)
+ADAPTIVE_SYMBOLS = ["tff_robust_pose_scenes_adaptive_dev", "tff_robust_pose_scenes_adaptive_host", "tff_robust_round_plan"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -189,6 +197,48 @@ RAGGED_METHODS = ("LinearTFTPoseEstimation", "LinearFPoseEstimation", "OptimFPos
 
 # methods the robust estimator (Context.robust_pose) draws its hypotheses and refits with, and their minimal sample
 ROBUST_METHODS = {"LinearTFTPoseEstimation": 7, "LinearFPoseEstimation": 8}
+
+
+MAX_ROUNDS = 32              # rounds of the adaptive robust call (tff_robust_round_plan)
+
+
+def _check_adaptive(confidence, first_round):
+    """the adaptive arguments of robust_pose / robust_pose_scenes, refused as the library refuses them"""
+    c = float(confidence)
+    if not (0.0 < c < 1.0):
+        raise ValueError("confidence must lie strictly between 0 and 1, not %r" % (confidence,))
+    f = int(first_round)
+    if f != first_round or f < 4 or f % 4 != 0 or f > 0x7FFFFFFC:
+        raise ValueError("first_round must be a multiple of 4 and at least 4, not %r" % (first_round,))
+    return c, f
+
+
+def round_plan(confidence, n_hyp, first_round=256):
+    """tff_robust_round_plan: (ends (R,) int64, qmin (R,) float64) of the adaptive robust call -- round r ends at ends[r - 1] =
+    min(n_hyp, first_round << (r - 1)) hypotheses per scene, where a scene stops once adaptive_stop(...) holds at qmin[r - 1] =
+    -expm1(log1p(-confidence) / ends[r - 1]).  Needs no context and no GPU."""
+    c, f = _check_adaptive(confidence, first_round)
+    if int(n_hyp) != n_hyp or int(n_hyp) < 1:
+        raise ValueError("n_hyp must be an integer of at least 1")
+    lib = load_library()
+    ends = np.zeros(MAX_ROUNDS, dtype=np.int64); qmin = np.zeros(MAX_ROUNDS); rounds = ctypes.c_int32(0)
+    _check(lib, lib.tff_robust_round_plan(c, int(n_hyp), f, ctypes.c_void_p(ends.ctypes.data), ctypes.c_void_p(qmin.ctypes.data),
+                                          ctypes.cast(ctypes.byref(rounds), ctypes.c_void_p)), "tff_robust_round_plan")
+    return ends[:rounds.value].copy(), qmin[:rounds.value].copy()
+
+
+def adaptive_stop(best, ns, n_sample, qmin, msac=False):
+    """The stop rule of the adaptive robust call in numpy, decision for decision what the device computes: best = the largest count (score with msac)
+    of the scene so far (-1: no success), ns its correspondences.  I = best (// SCORE_UNITS with msac); stop iff I >= 1 and (I / ns) multiplied by
+    itself n_sample - 1 times, in double, is >= qmin."""
+    I = int(best) // SCORE_UNITS if (msac and best >= 0) else int(best)
+    if I < 1:
+        return False
+    w = np.float64(I) / np.float64(ns)
+    q = w
+    for _ in range(int(n_sample) - 1):
+        q = q * w
+    return bool(q >= np.float64(qmin))
 
 
 def _splitmix64(x):
@@ -802,7 +852,8 @@ class Context:
                                                             float(threshold), self._p(mask), self._p(cnt)), "tff_inlier_mask_batch_dev")
         return (mask, cnt) if with_counts else mask
 
-    def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False):
+    def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False,
+                    confidence=None, first_round=256):
         """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
         best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
         Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
@@ -811,11 +862,16 @@ class Context:
         iter_refined, status_refined.  polish=True: BundleAdjustment on the pose and its inliers in one more call (bundle_adjust_ragged with the mask and the
         offsets [0, Ns], built on the device; no synchronisation and no copy on the device path), as R_t_2_polished, R_t_3_polished, iter_polished, repr_err_polished, status_polished.
         After set_score("msac") the hypotheses are ranked, refits adopted and the winner picked by the MSAC score, and `score` joins the dict: that of the
-        returned pose, from one more inlier_count call (0-d CUDA tensor, no synchronisation / int; -1 without a pose).  mask and inliers stay the hard rule."""
+        returned pose, from one more inlier_count call (0-d CUDA tensor, no synchronisation / int; -1 without a pose).  mask and inliers stay the hard rule.
+        confidence = c in (0, 1): the early stop of robust_pose_scenes for this one scene (the S = 1 call with the offsets [0, Ns]): n_hyp is the cap,
+        first_round the first round's length, and n_hyp_used joins the dict; the result is that of this call with n_hyp = n_hyp_used."""
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
             raise ValueError("unknown refine method %r" % (refine,))
+        if confidence is not None:
+            return self._robust_pose_adaptive(method, scene, calm, n_hyp, threshold, seed, n_sample, candidates, lo_rounds, refine, polish,
+                                              *_check_adaptive(confidence, first_round))
         mid = METHOD_IDS[method]
         ns = 0 if n_sample is None else int(n_sample)
         args = (int(seed), int(n_hyp), ns, float(threshold), int(candidates), int(lo_rounds))
@@ -872,6 +928,46 @@ class Context:
                 self._polish(out, calm, scene, torch.arange(2, dtype=torch.int64, device=dev) * Ns, True)   # [0, Ns], made on the device
         return out
 
+    def _robust_pose_adaptive(self, method, scene, calm, n_hyp, threshold, seed, n_sample, candidates, lo_rounds, refine, polish, confidence, first_round):
+        """robust_pose with a confidence: the S = 1 scenes call, reshaped to the one-scene dict; refine and polish as robust_pose does them"""
+        host = isinstance(scene, np.ndarray)
+        if host:
+            sc = np.ascontiguousarray(scene, dtype=np.float64)
+            if sc.ndim != 2 or sc.shape[1] != 6:
+                raise ValueError("scene must be (Ns, 6)")
+            Ns = sc.shape[0]
+            offsets = np.array([0, Ns], dtype=np.int64)
+            if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) != (9, 3):
+                raise ValueError("CalM must be (9, 3)")
+        else:
+            if not (scene.is_cuda and scene.dtype == torch.float64 and scene.is_contiguous() and scene.dim() == 2 and scene.shape[1] == 6):
+                raise ValueError("scene must be a contiguous float64 CUDA tensor of shape (Ns, 6)")
+            if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) != (9, 3):
+                raise ValueError("CalM must be (9, 3)")
+            sc = scene; Ns = scene.shape[0]
+            if isinstance(calm, np.ndarray):
+                calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
+            calm = calm.to(device=scene.device, dtype=torch.float64)
+            offsets = torch.arange(2, dtype=torch.int64, device=scene.device) * Ns      # [0, Ns], made on the device
+        r = self.robust_pose_scenes(method, sc, offsets, calm, n_hyp, threshold, seed=seed, n_sample=n_sample, candidates=candidates, lo_rounds=lo_rounds,
+                                    ns_max=Ns, confidence=confidence, first_round=first_round)
+        one = (lambda a: a[0].item()) if host else (lambda a: a[0])
+        out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
+                   refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
+        if "score" in r:
+            out["score"] = one(r["score"])
+        out["n_hyp_used"] = one(r["n_hyp_used"])
+        if refine is not None:                                               # (boolean indexing reads the count on the host)
+            inl = sc[r["mask"] != 0] if host else sc[r["mask"] != 0].contiguous()
+            f = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
+            out.update(R_t_2_refined=f["R_t_2"][0], R_t_3_refined=f["R_t_3"][0], T_refined=f["T"][0], iter_refined=f["iter"][0],
+                       status_refined=f["status"][0])
+        if polish:
+            self._polish(out, calm, sc, offsets, True)
+            if host:
+                out["iter_polished"] = int(out["iter_polished"]); out["status_polished"] = int(out["status_polished"])
+                out["repr_err_polished"] = float(out["repr_err_polished"])
+        return out
 
     def _calm_scenes(self, calm, S, dev):
         """(9, 3) or (S, 9, 3) numpy / torch CalM -> (column-major flat tensor on dev, calm_stride)"""
@@ -886,7 +982,7 @@ class Context:
         return calm_cm.to(device=dev, dtype=torch.float64), stride
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
-                           polish=False, refine=None):
+                           polish=False, refine=None, confidence=None, first_round=256):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
@@ -899,7 +995,12 @@ class Context:
         (S,3,4), T_refined (S,3,3,3), iter_refined, status_refined (S,): bit for bit what robust_pose(..., refine=...) gives for the scene alone; a scene
         without a pose has no inliers and gets ST_TOO_FEW and NaN.  On the device path the inliers are packed without reading a count (no
         synchronisation when ns_max is passed).  The polish keeps starting from the robust poses.
-        After set_score("msac"): as robust_pose, with `score` (S,) from one more inlier_count_scenes call, -1 for a scene without a pose."""
+        After set_score("msac"): as robust_pose, with `score` (S,) from one more inlier_count_scenes call, -1 for a scene without a pose.
+        confidence = c in (0, 1): the early stop (tff_robust_pose_scenes_adaptive_*).  Hypotheses are drawn in rounds ending at round_plan(c, n_hyp,
+        first_round)[0] per scene, n_hyp being the cap, and a scene stops after the round at which adaptive_stop holds for its best hypothesis; n_hyp_used
+        (S,) int32 joins the dict (0 for a scene that never ran), and scene s gets bit for bit what robust_pose gives for it alone with n_hyp =
+        n_hyp_used[s] and seed + s.  Still no synchronisation on the device path.  Without a confidence nothing changes and the key is absent."""
+        adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
         if refine is not None and refine not in RAGGED_METHODS:
             raise ValueError("robust_pose_scenes refines with one of %s, not %r" % (", ".join(RAGGED_METHODS), refine))
         if method not in ROBUST_METHODS:
@@ -921,12 +1022,20 @@ class Context:
             Rt2 = np.empty((S, 12)); Rt3 = np.empty((S, 12)); T = np.empty((S, 27))
             mask = np.zeros(sc.shape[0], dtype=np.uint8); info = np.zeros((S, 4), dtype=np.int32); st = np.zeros(S, dtype=np.int32)
             ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
-            _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
-                                                                  ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
+            if adaptive is None:
+                _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
+                                                                      ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
+            else:
+                used = np.zeros(S, dtype=np.int32)
+                _check(self.lib, self.lib.tff_robust_pose_scenes_adaptive_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args,
+                                                                               *adaptive, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(used),
+                                                                               ptr(st)), "tff_robust_pose_scenes_adaptive_host")
             assert ntot <= mask.shape[0]
             out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
                        T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
                        candidates=info[:, 3], status=st)
+            if adaptive is not None:
+                out["n_hyp_used"] = used
             if getattr(self, "_score", 0):
                 sco = self.inlier_count_scenes(sc, offsets, calm, out["R_t_2"], out["R_t_3"], threshold).cpu().numpy() if S else np.zeros(0, dtype=np.int32)
                 out["score"] = np.where(st == 0, sco, -1).astype(np.int32)
@@ -954,11 +1063,20 @@ class Context:
         mask = torch.empty(ntot, dtype=torch.uint8, device=dev)
         info = torch.empty((S, 4), dtype=torch.int32, device=dev); st = torch.empty(S, dtype=torch.int32, device=dev)
         self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
-                                                             stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
-                                                             self._p(st)), "tff_robust_pose_scenes_dev")
+        if adaptive is None:
+            _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
+                                                                 stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
+                                                                 self._p(st)), "tff_robust_pose_scenes_dev")
+        else:
+            used = torch.zeros(S, dtype=torch.int32, device=dev)
+            _check(self.lib, self.lib.tff_robust_pose_scenes_adaptive_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S,
+                                                                          self._p(calm_cm), stride, *args, *adaptive, self._p(Rt2), self._p(Rt3), self._p(T),
+                                                                          self._p(mask), self._p(info), self._p(used), self._p(st)),
+                   "tff_robust_pose_scenes_adaptive_dev")
         out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
                    mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        if adaptive is not None:
+            out["n_hyp_used"] = used
         if getattr(self, "_score", 0):                                       # one more count call on the returned poses; no pose (NaN): -1
             sco = self.inlier_count_scenes(scenes, offsets, calm, out["R_t_2"], out["R_t_3"], threshold) if S else torch.zeros_like(st)
             out["score"] = torch.where(st == 0, sco, torch.full_like(sco, -1))

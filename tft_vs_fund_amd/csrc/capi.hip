@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <climits>
 #include <cstring>
+#include <cmath>
 #include "../../include/tftfund.h"
 #include "launch.h"
 #include "ragged_kernel.h"
@@ -886,11 +887,32 @@ int launch_robust(tff_ctx* c, const RaggedRoute& route, const RobustCall& q) {
 }
 
 // ---- robust estimation for a batch of scenes (tff_robust_pose_scenes_*, tff_inlier_count_scenes_dev; kernels in robust_scenes_kernel.h) -----------------
+struct RoundPlan;
 struct ScenesCall {
     int32_t method; const double* scenes; const int64_t* offsets; int64_t n_total; int32_t ns_max; int64_t S; const double* calm; int64_t calm_stride;
     uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold; int32_t n_cand; int32_t lo_rounds;
     double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
+    const RoundPlan* plan = nullptr;         // tff_robust_pose_scenes_adaptive_*: the rounds, and ...
+    int32_t* used = nullptr;                 // ... S: the hypotheses each scene drew
 };
+// The rounds of the adaptive call (include/tftfund.h): round r ends at ends[r - 1] = min(n_hyp, first_round << (r - 1)) hypotheses per scene, and a scene
+// stops there once w^n_sample >= qmin[r - 1] = -expm1(log1p(-confidence) / ends[r - 1]) for the inlier ratio w of its best hypothesis
+constexpr int MAX_ROUNDS = 32;
+struct RoundPlan { int rounds; int64_t ends[MAX_ROUNDS]; double qmin[MAX_ROUNDS]; };
+int make_round_plan(double confidence, int64_t n_hyp, int32_t first_round, RoundPlan* p) {
+    if (!(confidence > 0.0 && confidence < 1.0)) return fail(TFF_E_INVALID, "robust estimation: the confidence must lie strictly between 0 and 1");
+    if (first_round < 4 || first_round % 4 != 0) return fail(TFF_E_INVALID, "robust estimation: first_round must be a multiple of 4 and at least 4");
+    if (n_hyp < 1) return fail(TFF_E_INVALID, "robust estimation: n_hyp must be at least 1");
+    const double lg = std::log1p(-confidence);
+    for (int r = 0; r < MAX_ROUNDS; ++r) {
+        const int64_t grown = (int64_t)first_round << r;                     // (at most 2^31 << 31)
+        const int64_t e = grown < n_hyp ? grown : n_hyp;
+        p->ends[r] = e;
+        p->qmin[r] = -std::expm1(lg / (double)e);
+        if (e == n_hyp) { p->rounds = r + 1; return 0; }
+    }
+    return fail(TFF_E_INVALID, "robust estimation: more than 32 rounds between first_round and n_hyp");
+}
 // what can be refused without the offsets: check_robust's list (the scene size apart: too few correspondences is a per-scene status here) and the sizes
 int check_scenes(const tff_ctx* c, ScenesCall* q, const RaggedRoute** route) {
     RobustCall r{q->method, q->scenes, INT32_MAX, q->calm, q->seed, q->n_hyp, q->n_sample, q->threshold, q->n_cand, q->lo_rounds,
@@ -910,7 +932,7 @@ int check_scenes(const tff_ctx* c, ScenesCall* q, const RaggedRoute** route) {
 }
 // the inlier counts of B hypotheses, hypothesis b being g = first + b of the call and belonging to scene g / per
 int launch_count_scenes(tff_ctx* c, const tff::SceneSet& set, const double* Rt2, const double* Rt3, int64_t first, int64_t B, int64_t per, double threshold,
-                        int32_t* counts) {
+                        int32_t* counts, const int32_t* live = nullptr) {
     const long rows = tff::SCENES_COUNT_ROWS;
     long grid = (B + rows - 1) / rows;
     if (grid > 256L * 2) grid = 256L * 2;                                    // two workgroups per CU
@@ -921,6 +943,7 @@ int launch_count_scenes(tff_ctx* c, const tff::SceneSet& set, const double* Rt2,
     tff::ScenesCountArgs a{set, Rt2, Rt3, (long)first, (long)B, (long)per, slab, threshold, counts, stage};
     const bool msac = c->score == 1;
     if (msac) a.score_c = score_scale(threshold);
+    a.live = live;
     return launch(c, msac ? tff::k_inlier_count_scenes_msac : tff::k_inlier_count_scenes, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, ((size_t)36 * rows + (size_t)stage) * sizeof(double), a);
 }
 // device pointers; the lock is held and the context's device current
@@ -929,6 +952,27 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     const int K = q.n_cand, n = q.n_sample;
     const int64_t S = q.S, G = S * q.n_hyp, C = S * K;
     const tff::SceneSet set{q.scenes, (const long*)q.offsets, (long)S, (long)q.n_total, q.ns_max, n, q.calm, (long)q.calm_stride};
+    // one chunk of hypotheses: the fixed call cuts g = s * n_hyp + h, the adaptive call the rows of a round (its longest round sizes the chunk)
+    int64_t rows_max = G;
+    if (q.plan) {
+        rows_max = 0;
+        for (int r = 0; r < q.plan->rounds; ++r) {
+            const int64_t len = q.plan->ends[r] - (r ? q.plan->ends[r - 1] : 0);
+            if (S * len > rows_max) rows_max = S * len;
+        }
+    }
+    const int64_t chunk = rows_max < tff::ROBUST_CHUNK ? rows_max : tff::ROBUST_CHUNK;
+    const size_t hyp_bytes = align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * 27 * sizeof(double)) +
+                             align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)chunk * n * sizeof(int32_t));
+    // ... and behind it, for the adaptive call: the round's dense counts | best (S x 8) | live (S x 4)
+    const size_t round_bytes = q.plan ? align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)S * 8) + align256((size_t)S * 4) : 0;
+    if (q.plan) {                                                            // every workspace of the call before its first launch: none grows between two rounds
+        TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
+        TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
+        void* before = c->retry.p;                                           // (the row kernels' retry list, retry_list_begin: sized by the largest chunk)
+        TFF_TRY(c->retry.reserve(((size_t)chunk + 2) * sizeof(int32_t)));
+        if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
+    }
     if (q.n_total) TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
     // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate | flags | the packed refit batch
     size_t off = 0;
@@ -955,19 +999,19 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     int32_t* c_idx = (int32_t*)(cp + o_idx);
     double* c_calm = (double*)(cp + o_calm);
     const tff::ScenesFinishArgs fin{st, q.Rt2, q.Rt3, q.T, q.info, q.status};
-    if (q.n_total == 0)                                                      // no scene can be valid, and the pose kernels must not gather from an empty array
+    if (q.n_total == 0) {                                                    // no scene can be valid, and the pose kernels must not gather from an empty array
+        if (q.plan) TFF_HIP(hipMemsetAsync(q.used, 0, (size_t)S * sizeof(int32_t), c->stream));
         return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
+    }
 
     // one chunk of hypotheses: poses (51 doubles) | CalM (27) | status | sample indices
-    const int64_t chunk = G < tff::ROBUST_CHUNK ? G : tff::ROBUST_CHUNK;
-    TFF_TRY(c->robust_hyp.reserve(align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * 27 * sizeof(double)) +
-                                  align256((size_t)chunk * sizeof(int32_t)) + (size_t)chunk * n * sizeof(int32_t)));
+    TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
     TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
     char* hp = (char*)c->robust_hyp.p;
     double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
     double* h_calm = (double*)hp;                hp += align256((size_t)chunk * 27 * sizeof(double));
     int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
-    int32_t* h_idx = (int32_t*)hp;
+    int32_t* h_idx = (int32_t*)hp;               hp += align256((size_t)chunk * n * sizeof(int32_t));
     int32_t* counts = (int32_t*)c->robust_counts.p;
 
     // the method's *_pose_sampled_dev on the packed array: global indices, one CalM per row
@@ -976,8 +1020,35 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         p.sample_idx = idx; p.sample_ns = (int32_t)q.n_total;
         return m.launch(c, p);
     };
+    // 1a. the adaptive call: round r draws the hypotheses [e_prev, e_end) of the scenes that are still live, chunk by chunk over the round's rows
+    //     g' = s * len + i; the counts land where the fixed call puts them (stride n_hyp, -1 where nothing was drawn), the rule closes the round
+    if (q.plan) {
+        int32_t* dense = (int32_t*)hp;               hp += align256((size_t)chunk * sizeof(int32_t));
+        unsigned long long* best = (unsigned long long*)hp;   hp += align256((size_t)S * 8);
+        int32_t* live = (int32_t*)hp;
+        const tff::RoundState rs{set, live, best, q.used};
+        const unsigned sgrid = (unsigned)((S + 255) / 256);
+        TFF_HIP(hipMemsetAsync(counts, 0xFF, (size_t)G * sizeof(int32_t), c->stream));
+        TFF_TRY(launch(c, tff::k_round_init, sgrid, 256, 0, rs));
+        int64_t e_prev = 0;
+        for (int r = 0; r < q.plan->rounds; ++r) {
+            const int64_t e_end = q.plan->ends[r], len = e_end - e_prev, Gr = S * len;
+            for (int64_t first = 0; first < Gr; first += chunk) {
+                const int64_t B = Gr - first < chunk ? Gr - first : chunk;
+                TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
+                               tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)len, n, h_idx, h_calm, (long)e_prev, live}));
+                TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
+                TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, len, q.threshold, dense, live));
+                TFF_TRY(launch(c, tff::k_round_scatter, (unsigned)((B + 255) / 256), 256, 0,
+                               tff::RoundScatterArgs{dense, h_status, (long)first, (long)B, (long)len, (long)e_prev, (long)q.n_hyp, live, best, counts}));
+            }
+            TFF_TRY(launch(c, tff::k_round_close, sgrid, 256, 0,
+                           tff::RoundCloseArgs{rs, (long)e_end, q.plan->qmin[r], n, c->score == 1 ? TFF_SCORE_UNITS : 1}));
+            e_prev = e_end;
+        }
+    }
     // 1. hypotheses and their counts, chunk by chunk over g = s * n_hyp + h
-    for (int64_t first = 0; first < G; first += chunk) {
+    for (int64_t first = 0; !q.plan && first < G; first += chunk) {
         const int64_t B = G - first < chunk ? G - first : chunk;
         TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
                        tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
@@ -1026,7 +1097,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 103; }
+int tff_version(void) { return 104; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1275,10 +1346,11 @@ int tff_robust_pose_scenes_dev(tff_ctx* c, int32_t method, const double* scenes,
 }
 
 // host pointers: the offsets are checked here, n_total and ns_max come from them; H2D, the _dev path, D2H, one synchronisation
-int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
-                                int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
-                                double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
-    TFF_ENTER(c);
+// (the lock is held.  confidence: null for the fixed form; else the adaptive form's, with first_round and used)
+static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                              int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
+                              double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status, const double* confidence,
+                              int32_t first_round, int32_t* used) {
     if (S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
     if (!scene_offsets) return fail(TFF_E_INVALID, "null offsets");
     if (scene_offsets[0] < 0) return fail(TFF_E_INVALID, "robust estimation: negative offset");
@@ -1294,6 +1366,12 @@ int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes
                  Rt2, Rt3, T, mask, info, status};
     const RaggedRoute* route;
     TFF_TRY(check_scenes(c, &h, &route));
+    RoundPlan plan;
+    if (confidence) {
+        TFF_TRY(make_round_plan(*confidence, n_hyp, first_round, &plan));
+        if (!used) return fail(TFF_E_INVALID, "null pointer");
+        h.plan = &plan;
+    }
     if (S == 0) return 0;
     TFF_HIP(hipSetDevice(c->device));
     const size_t nscene = (size_t)n_total * 6 * sizeof(double), ncal = (size_t)(calm_stride ? S : 1) * 27 * sizeof(double), nS = (size_t)S;
@@ -1301,11 +1379,11 @@ int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes
     TFF_TRY(c->calm.reserve(ncal));
     TFF_TRY(c->ragged_off.reserve((nS + 1) * sizeof(int64_t)));
     TFF_TRY(c->out.reserve(nS * 51 * sizeof(double) + (size_t)n_total + 8));
-    TFF_TRY(c->idx.reserve(nS * 5 * sizeof(int32_t)));
+    TFF_TRY(c->idx.reserve(nS * 6 * sizeof(int32_t)));
     ScenesCall d = h;
     d.scenes = (const double*)c->in.p; d.calm = (const double*)c->calm.p; d.offsets = (const int64_t*)c->ragged_off.p;
     d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + nS * 12; d.T = d.Rt3 + nS * 12; d.mask = (uint8_t*)(d.T + nS * 27);
-    d.info = (int32_t*)c->idx.p; d.status = d.info + nS * 4;
+    d.info = (int32_t*)c->idx.p; d.status = d.info + nS * 4; d.used = d.status + nS;
     if (nscene) TFF_HIP(hipMemcpyAsync(c->in.p, scenes, nscene, hipMemcpyHostToDevice, c->stream));
     TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
     TFF_HIP(hipMemcpyAsync(c->ragged_off.p, scene_offsets, (nS + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -1316,8 +1394,53 @@ int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes
     if (n_total) TFF_HIP(hipMemcpyAsync(mask, d.mask, (size_t)n_total, hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipMemcpyAsync(info, d.info, nS * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipMemcpyAsync(status, d.status, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (confidence) TFF_HIP(hipMemcpyAsync(used, d.used, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipStreamSynchronize(c->stream));
     return 0;
+}
+int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                                int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
+                                double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
+    TFF_ENTER(c);
+    return robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
+                              info, status, nullptr, 0, nullptr);
+}
+
+// the adaptive forms: the fixed forms' checks, then the plan of rounds (its refusals: confidence, first_round, more than 32 rounds) and `used`
+int tff_robust_round_plan(double confidence, int64_t n_hyp, int32_t first_round, int64_t* ends, double* qmin, int32_t* rounds) {
+    if (!ends || !qmin || !rounds) return fail(TFF_E_INVALID, "null pointer");
+    RoundPlan p;
+    TFF_TRY(make_round_plan(confidence, n_hyp, first_round, &p));
+    for (int r = 0; r < p.rounds; ++r) { ends[r] = p.ends[r]; qmin[r] = p.qmin[r]; }
+    *rounds = p.rounds;
+    return 0;
+}
+
+int tff_robust_pose_scenes_adaptive_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max,
+                                        int64_t S, const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold,
+                                        int32_t n_cand, int32_t lo_rounds, double confidence, int32_t first_round, double* Rt2, double* Rt3, double* T,
+                                        uint8_t* mask, int32_t* info, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_scenes(c, &q, &route));
+    RoundPlan plan;
+    TFF_TRY(make_round_plan(confidence, n_hyp, first_round, &plan));
+    if (!used) return fail(TFF_E_INVALID, "null pointer");
+    q.plan = &plan; q.used = used;
+    if (S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    return launch_robust_scenes(c, *route, q);
+}
+
+int tff_robust_pose_scenes_adaptive_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                                         int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
+                                         int32_t lo_rounds, double confidence, int32_t first_round, double* Rt2, double* Rt3, double* T, uint8_t* mask,
+                                         int32_t* info, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    return robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
+                              info, status, &confidence, first_round, used);
 }
 
 int tff_inlier_count_scenes_dev(tff_ctx* c, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int64_t S, const double* calm,

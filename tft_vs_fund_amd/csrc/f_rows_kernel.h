@@ -306,7 +306,8 @@ __device__ __forceinline__ void linear_f_pose_rows_exact(const LinearTftArgs& a)
         const int N = RAGGED ? rows_ragged_n(a, blk) : opaque_int(a.N);
         const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         int status;
-        if (N < 8) {                                                         // linearF.m:35-37
+        const bool dead = !RAGGED && !wave_any(!j.bad_index);                // sampled hypotheses, all four rows outside the scene: tft_rows_exact_kernel.h
+        if (N < 8 || dead) {                                                 // linearF.m:35-37
             status = ST_TOO_FEW;
             rows_store_nan<RAGGED>(a, j, N);
         } else {

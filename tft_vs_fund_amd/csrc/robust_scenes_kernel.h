@@ -10,6 +10,7 @@
 //   k_scenes_offsets       offsets of the S * K + 1 packed refit items: a one-workgroup scan
 //   k_scenes_compact       k_robust_compact with a scene lookup
 //   k_scenes_finish        k_robust_finish per scene, and the outputs of an invalid scene
+//   k_round_init / k_round_scatter / k_round_close   the adaptive call (tff_robust_pose_scenes_adaptive_*): rounds of hypotheses and the stop rule
 //
 // k_robust_mark, k_robust_topk (gridDim.y = S), k_robust_seed and k_robust_adopt (robust_kernel.h) serve both paths.  A chunk of ROBUST_CHUNK
 // hypotheses may cut a scene anywhere: every kernel derives (s, h) from g.
@@ -50,15 +51,17 @@ struct ScenesSampleArgs {
     int n;
     int* out;                // B x n indices into the packed array, -1 for an invalid scene
     double* calm_out;        // B x 27: the row's CalM, for the pose kernels (calm_stride 27)
+    long hyp_base;           // a round of the adaptive call (per = the round's length): the row's hypothesis is hyp_base + g % per; 0 otherwise
+    const int* live;         // null, or S: a scene with live[s] == 0 gets indices -1, like an invalid one
 };
 __global__ void __launch_bounds__(256) k_scenes_sample(const ScenesSampleArgs a) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
     const long g = a.first + b;
     const long s = g / a.per;
-    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(g - s * a.per);
+    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(a.hyp_base + (g - s * a.per));
     long o; int ns;
-    const bool ok = scene_range(a.q, s, &o, &ns) == ST_OK;
+    const bool ok = scene_range(a.q, s, &o, &ns) == ST_OK && !(a.live && a.live[s] == 0);
     int* out = a.out + b * a.n;
     if (ok) sample_draw(a.seed + (unsigned long long)s, h, a.n, ns, (int)o, out);
     else for (int i = 0; i < a.n; ++i) out[i] = -1;
@@ -79,6 +82,7 @@ struct ScenesCountArgs {
     int* counts;             // B; -1 for a hypothesis of an invalid scene
     int stage_doubles;       // LDS doubles behind the cameras
     double score_c;          // k_inlier_count_scenes_msac only: 1 / (6 thr^2) from the host (blocks_kernel.h::inlier_weight); 0 for the count kernel
+    const int* live;         // null, or S: the segment of a scene with live[s] == 0 is skipped like an invalid scene's (-1)
 };
 constexpr int SCENES_COUNT_ROWS = 4 * INLIER_WG_WAVES;       // hypotheses a workgroup serves at a time
 constexpr int SCENES_STAGE_MIN = 8;                          // shorter segments read their scene through L2
@@ -131,7 +135,7 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_scenes
         long seg_end = (s + 1) * a.per - a.first;
         if (seg_end > slab_end) seg_end = slab_end;
         long o; int n;
-        if (scene_range(a.q, s, &o, &n) != ST_OK) {
+        if (scene_range(a.q, s, &o, &n) != ST_OK || (a.live && a.live[s] == 0)) {
             for (long i = b + thread_in_block(); i < seg_end; i += 64 * INLIER_WG_WAVES) a.counts[i] = -1;
         } else {
             const double* src = a.q.scenes + 6 * o;
@@ -152,6 +156,71 @@ __global__ void __launch_bounds__(64 * INLIER_WG_WAVES, 2) k_inlier_count_scenes
 }
 constexpr auto k_inlier_count_scenes = k_inlier_count_scenes_t<false>;   // (the pattern of blocks_kernel.h::k_repr_error_t)
 constexpr auto k_inlier_count_scenes_msac = k_inlier_count_scenes_t<true>;
+
+// ---- the adaptive call: hypotheses in rounds, a scene stops once its best hypothesis makes another all-inlier sample unnecessary ----------------------
+// Round r draws the hypotheses [e_prev, e_end) of every scene that is still live; the round's rows are g' = s * len + i (len = e_end - e_prev), cut
+// into chunks like the fixed call's.  k_round_scatter moves a chunk's dense counts to the scene-major array of the fixed call (stride n_hyp; the whole
+// array is -1 before round 1, so a hypothesis never drawn is never selected) and keeps the scene's best; k_round_close applies the rule once the round's
+// last chunk is in.  The rule has no log and no pow: q = w^n_sample by repeated multiplication against a threshold the host computed (include/tftfund.h).
+struct RoundState {
+    SceneSet q;
+    int* live;               // S: 1 while the scene draws
+    unsigned long long* best;   // S: the largest count so far + 1, 0 = no success yet (64 bits: the atomic maximum of k_robust_topk)
+    int* used;               // S: hypotheses drawn (the caller's array)
+};
+__global__ void __launch_bounds__(256) k_round_init(const RoundState a) {
+    const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.q.S) return;
+    long o; int n;
+    a.live[s] = scene_range(a.q, s, &o, &n) == ST_OK ? 1 : 0;
+    a.best[s] = 0ULL;
+    a.used[s] = 0;
+}
+struct RoundScatterArgs {
+    const int* dense;        // B counts of this chunk (k_inlier_count_scenes_t: -1 for a scene that is not live)
+    const int* status;       // B pose statuses
+    long first, B;           // row b of the chunk is g' = first + b of the round
+    long len;                // the round's hypotheses per scene
+    long e_prev;             // ... the first of them
+    long n_hyp;              // stride of `counts`
+    const int* live;
+    unsigned long long* best;
+    int* counts;             // S x n_hyp
+};
+__global__ void __launch_bounds__(256) k_round_scatter(const RoundScatterArgs a) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const long g = a.first + b;
+    const long s = g / a.len;
+    if (a.live[s] == 0) return;                                              // (its range of `counts` keeps what it holds: -1 beyond used[s])
+    const int c = a.status[b] != 0 ? -1 : a.dense[b];                        // k_robust_mark's rule
+    a.counts[s * a.n_hyp + a.e_prev + (g - s * a.len)] = c;
+    if (c >= 0) atomicMax(a.best + s, (unsigned long long)c + 1ULL);
+}
+struct RoundCloseArgs {
+    RoundState r;
+    long e_end;              // hypotheses per scene drawn after this round
+    double qmin;             // -expm1(log1p(-confidence) / e_end), from the host
+    int n_sample;
+    int units;               // 1, or TFF_SCORE_UNITS when the counts are MSAC scores: best / units is a lower bound on the inliers
+};
+// does a scene of n correspondences whose best hypothesis has I inliers stop at the threshold qmin?  (the numpy twin: api.adaptive_stop)
+__device__ __forceinline__ bool round_stops(const int I, const int n, const int n_sample, const double qmin) {
+    if (I < 1) return false;
+    const double w = (double)I / (double)n;
+    double q = w;
+    for (int k = 1; k < n_sample; ++k) q = q * w;
+    return q >= qmin;
+}
+__global__ void __launch_bounds__(256) k_round_close(const RoundCloseArgs a) {
+    const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.r.q.S || a.r.live[s] == 0) return;
+    long o; int n;
+    if (scene_range(a.r.q, s, &o, &n) != ST_OK) return;                      // (such a scene was never live: a guard)
+    a.r.used[s] = (int)a.e_end;
+    const int best = (int)a.r.best[s] - 1;
+    if (round_stops(best >= 0 ? best / a.units : -1, n, a.n_sample, a.qmin)) a.r.live[s] = 0;
+}
 
 // ---- per-correspondence inlier flags with a scene lookup ---------------------------------------------------------------------------------------
 struct ScenesMaskArgs {

@@ -181,7 +181,10 @@ __device__ __forceinline__ void linear_tft_pose_rows_exact(const LinearTftArgs& 
         const RowJob j = RAGGED ? rows_begin_ragged(a, w, blk) : rows_begin(a, w, blk, N);
         double* dbg = j.dbg;
         int status, hint = 0;
-        if (N < 7) {                                                         // experiments.m:99 (wave-uniform: N is the batch's)
+        // sampled hypotheses: a wavefront whose four rows all hold an index outside the scene (the rounds of tff_robust_pose_scenes_adaptive_* mark the
+        // hypotheses of a scene that has stopped that way) leaves here with what rows_pose_tail gives such rows, NaN and ST_TOO_FEW, and pays for no pose
+        const bool dead = !RAGGED && !wave_any(!j.bad_index);
+        if (N < 7 || dead) {                                                 // experiments.m:99 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
             rows_store_nan<RAGGED>(a, j, N);
         } else {
