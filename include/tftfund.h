@@ -402,7 +402,8 @@ int tff_robust_pose_host(tff_ctx* ctx, int32_t method, const double* scene, int3
  * Outputs: Rt2, Rt3 (S x 12), T (S x 27), mask (n_total bytes, the flags of scene s at mask[scene_offsets[s] ..]), info (S x 4), status (S).
  * THE CONTRACT: the outputs of scene s are bit for bit those of tff_robust_pose_dev on that scene alone -- its n_s correspondences, its CalM, the seed
  * seed + s in wrapping uint64 arithmetic, the same remaining arguments and context options.  Nothing depends on S, on the neighbouring scenes, or on where a
- * chunk of hypotheses (g = s * n_hyp + h, 262 144 per chunk) ends.
+ * chunk of hypotheses (g = s * n_hyp + h, 262 144 per chunk) ends.  (There is one implementation: tff_robust_pose_* is this call for S = 1, the scene
+ * [0, Ns) and the shared CalM, behind its own argument checks.  The sentence above says that a scene's result is independent of the list it stands in.)
  * Per-scene failures (the offsets of _dev are device data, so these are statuses, as in the ragged calls): n_s < n_sample gives TFF_ST_TOO_FEW; a decreasing
  * or negative offset, an offset above n_total or n_s > ns_max gives TFF_ST_BAD_OFFSETS; both with NaN poses, info = [0, -1, 0, 0] and zero flags, the
  * neighbours unaffected.  No successful hypothesis: TFF_ST_NO_POSE as above.  Whatever the offsets hold, no kernel reads or writes outside [0, n_total) of the
@@ -411,7 +412,7 @@ int tff_robust_pose_host(tff_ctx* ctx, int32_t method, const double* scene, int3
  * TFF_E_INVALID: what tff_robust_pose_dev refuses (the scene size apart), S < 0, S * n_hyp above 2^31 - 1, S * n_cand above the ragged call's 2^28 - 1 items,
  * a calm_stride other than 0 or 27, n_total or ns_max out of range; _host: decreasing or negative offsets, before any work.  S = 0 returns 0.
  * _dev: no host synchronisation and no device-to-host copy.  _host: host pointers (n_total and ns_max come from the offsets), one synchronisation.
- * Workspaces of the context, growing on demand: one chunk of hypotheses (78 doubles each), 4 * S * n_hyp bytes of counts, 49 * n_cand * n_total bytes for the
+ * Workspaces of the context, growing on demand: one chunk of hypotheses (51 doubles each, 78 with one CalM per scene), 4 * S * n_hyp bytes of counts, 49 * n_cand * n_total bytes for the
  * candidates' flags and packed refits (NOT S * n_cand * ns_max). */
 int tff_robust_pose_scenes_dev(tff_ctx* ctx, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max, int64_t S,
                                const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,

@@ -3,6 +3,9 @@ The glue of the many-scenes robust estimator (csrc/robust_scenes_kernel.h) on th
 and driven with six small scenes (5 .. 130 correspondences), slabs that cut scenes, a launch that starts inside a scene, malformed offsets and a packed
 batch smaller than the inliers.  References: api.sample_indices_reference for the sampler, the emulated k_repr_error per scene for the counts, numpy for
 offsets, compaction, the winner and the top-K order.  (Bit-identity with the one-scene call on the GPU is tests/test_gpu_robust_scenes.py.)
+The one-scene call is this chain with S = 1 and no offsets array (a null SceneSet::offsets = the scene [0, n_total)): the last test drives the sampler, the
+count kernel, the flags, offsets + compaction and the finish in that form against the same launch given [0, n] (the k_round_* kernels of the adaptive call
+never see null offsets: tests/test_emulated_adaptive.py).
 """
 import ctypes
 import os
@@ -175,3 +178,84 @@ def test_topk_order_with_the_scene_fields():
     order = [h for h in sorted(range(700), key=lambda h: (-cn[h], h)) if cn[h] >= 0][:5]
     assert [0xFFFFFFFF - (int(k) & 0xFFFFFFFF) for k in sel] == order
     assert [(int(k) >> 32) - 1 for k in sel] == [int(cn[h]) for h in order]
+
+
+def test_null_offsets_are_the_one_scene_zero_to_n_total():
+    """scene_range with offsets == null, through every kernel that calls it, against the same launch with the explicit offsets [0, n]: n = 7 (exactly one
+    sample), 256 and 257 (the compaction tile), K = 4 with candidates 1 and 2 absent; the sampler also without calm_out (the shared CalM); the count kernel
+in place and staged."""
+    L = _lib()
+    K, n_s, thr = 4, 7, 4.0
+    for n in (7, 256, 257):
+        scene, CalM, Rt0 = _synth(n, 40 + n)
+        calm = np.ascontiguousarray(CalM.T).reshape(27)
+        rng = np.random.default_rng(n)
+
+        def both(run):
+            """run(offsets) with null and with [0, n]: the two tuples of outputs must be equal array for array"""
+            got, ref = run(None), run(np.array([0, n], dtype=np.int64))
+            assert len(got) == len(ref)
+            for i, (g, r) in enumerate(zip(got, ref)):
+                assert np.array_equal(g, r), (n, run.__name__, i)
+            return got
+
+        def sset(off):
+            return (P(scene), P(off), c_l(1), c_l(n), c_i(n), c_i(n_s), P(calm), c_l(0))
+
+        # the sampler: a chunk of hypotheses (with and without calm_out), then the candidates' form with a key of 0
+        def sample(off):
+            outs = []
+            for with_calm in (True, False):
+                out = np.full((50, n_s), -7, dtype=np.int32); calm_out = np.full((50, 27), -3.0)
+                L.e_sample(*sset(off), c_u(99), c_l(5), None, c_l(50), c_l(1000), c_i(n_s), P(out), P(calm_out) if with_calm else None)
+                outs += [out, calm_out]
+            keys = np.array([(5 << 32) | (0xFFFFFFFF - h) for h in (3, 0, 17, 999)], dtype=np.uint64); keys[1] = 0
+            out = np.full((K, n_s), -7, dtype=np.int32)
+            L.e_sample(*sset(off), c_u(99), c_l(0), P(keys), c_l(K), c_l(K), c_i(n_s), P(out), None)
+            return outs + [out]
+        idx, copied, idx_alone, untouched, cand_idx = both(sample)
+        assert np.array_equal(idx, api.sample_indices_reference(99, 5, 50, n_s, n)) and np.array_equal(idx, idx_alone)
+        assert (copied == calm).all() and (untouched == -3.0).all()            # null calm_out: nothing is written
+        assert np.array_equal(cand_idx[2], api.sample_indices_reference(99, 17, 1, n_s, n)[0])
+        assert np.array_equal(cand_idx[1], api.sample_indices_reference(99, 0, 1, n_s, n)[0])
+
+        # flags of the K candidates, two of them absent
+        Rt2 = np.stack([_cm(Rt0[0] + rng.normal(0, 1e-3 * r, (3, 4))) for r in range(K)])
+        Rt3 = np.stack([_cm(Rt0[1] + rng.normal(0, 1e-3 * r, (3, 4))) for r in range(K)])
+        cnt = np.array([30, -1, -1, 20], dtype=np.int32)
+
+        def flags(off):
+            mask = np.full(K * n, 9, dtype=np.uint8); mcnt = np.full(K, -5, dtype=np.int32)
+            L.e_mask(*sset(off), P(Rt2), P(Rt3), c_l(K), c_l(K), c_d(thr), P(mask), P(mcnt), P(cnt), None)
+            return mask, mcnt
+        mask, mcnt = both(flags)
+        rows = mask.reshape(K, n)
+        assert (rows[1:3] == 9).all() and rows[0].max() <= 1 and int(rows[0].sum()) == mcnt[0] > 0 and int(rows[3].sum()) == mcnt[3]
+
+        # the count kernel: the K rows read in place, sixteen rows (a segment long enough to stage the scene in LDS); its integers are the row sums
+        def count(off):
+            outs = []
+            for rep in (1, 4):
+                r2 = np.ascontiguousarray(np.tile(Rt2, (rep, 1))); r3 = np.ascontiguousarray(np.tile(Rt3, (rep, 1))); B = K * rep
+                counts = np.full(B, -9, dtype=np.int32)
+                L.e_count(*sset(off), P(r2), P(r3), c_l(0), c_l(B), c_l(B), c_l(16), c_d(thr), P(counts), c_i(6 * n))
+                outs.append(counts)
+            return outs
+        c4, c16 = both(count)
+        assert c4[0] == mcnt[0] and c4[3] == mcnt[3] and np.array_equal(c16, np.tile(c4, 4))
+
+        # offsets + compaction + the winner
+        pose = rng.normal(size=K * 51); seed_idx = np.arange(K, dtype=np.int32) + 100; nref = np.arange(K, dtype=np.int32) % 3
+
+        def cand(off):
+            offsets = np.full(K + 1, -1, dtype=np.int64); packed = np.full((K * n, 6), -1.0)
+            o2 = np.zeros((1, 12)); o3 = np.zeros((1, 12)); oT = np.zeros((1, 27)); info = np.zeros((1, 4), dtype=np.int32)
+            status = np.full(1, -1, dtype=np.int32)
+            L.e_cand(*sset(off), c_i(K), P(cnt), P(seed_idx), P(nref), P(pose), P(mask), P(mcnt), P(offsets), P(packed), c_l(K * n),
+                     P(o2), P(o3), P(oT), P(info), P(status))
+            return offsets, packed, o2, o3, oT, info, status
+        offsets, packed, o2, o3, oT, info, status = both(cand)
+        assert offsets.tolist() == [0, mcnt[0], mcnt[0], mcnt[0], mcnt[0] + mcnt[3]]
+        assert np.array_equal(packed[:offsets[1]], scene[rows[0] != 0]) and np.array_equal(packed[offsets[3]:offsets[4]], scene[rows[3] != 0])
+        assert status.tolist() == [0] and info[0].tolist() == [30, 100, 0, 2]
+        assert np.array_equal(o2[0], pose[:12]) and np.array_equal(o3[0], pose[K * 12:K * 12 + 12]) and np.array_equal(oT[0], pose[K * 24:K * 24 + 27])

@@ -340,3 +340,90 @@ def test_refine_is_the_fixed_n_call_on_the_inliers():
     host = ctx.robust_pose("LinearTFTPoseEstimation", scene, CalM, 5000, 4.0, seed=2, refine="ResslTFTPoseEstimation")
     for k in ("R_t_2", "R_t_3", "T"):
         assert np.array_equal(_bits(host[k + "_refined"]), _bits(ref[k][0])), k
+
+
+# ---- the one-scene call is the scene-list chain at S = 1 ----------------------------------------------------------------------------------------------
+def _small_scene(n, clean):
+    """the config-4 recipe at n correspondences (a quarter displaced); clean: no noise and nothing displaced, so that a sample of all n has a pose"""
+    from tft_vs_fund_amd.scenes import generate_scene_batch
+    C, CalM, _, _ = generate_scene_batch(1, n, noise=0.0 if clean else 0.5, seed=11 + n)
+    scene = C[0].copy()
+    if not clean:
+        rng = np.random.default_rng(n)
+        bad = rng.choice(n, n // 4, replace=False)
+        scene[bad, 2:6] += rng.uniform(20, 80, size=(bad.size, 4))
+    return np.ascontiguousarray(scene), np.ascontiguousarray(CalM)
+
+
+def _np(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _assert_same_result(got, ref, what, keys=("mask", "inliers", "hypothesis", "refits", "candidates", "status")):
+    """two result dicts of the same shapes: poses and T as bit patterns, everything else exactly"""
+    for k in ("R_t_2", "R_t_3", "T"):
+        assert np.array_equal(_bits(got[k]), _bits(ref[k])), (what, k)
+    for k in keys + (("score",) if "score" in ref else ()):
+        assert np.array_equal(_np(got[k]), _np(ref[k])), (what, k, _np(got[k]), _np(ref[k]))
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("method", METHODS)
+def test_one_scene_call_equals_the_explicit_one_scene_list(method):
+    """robust_pose (device tensors: no offsets reach the library; numpy: the offsets {0, Ns} are made by the library) against robust_pose_scenes with the
+    explicit offsets [0, Ns] and the shared (9, 3) CalM, bit for bit.  Ns = one sample, 65 and 257; 5 hypotheses for 16 candidates (keys of 0 reach seed,
+    offsets, compaction and finish), 1 000 hypotheses without and with refits; under both scores."""
+    from tft_vs_fund_amd import api
+    ctx = _ctx()
+    n = api.ROBUST_METHODS[method]
+    try:
+        for score in ("count", "msac"):
+            ctx.set_score(score)
+            for Ns in (n, 65, 257):
+                scene, CalM = _small_scene(Ns, clean=Ns == n)
+                d_scene = torch.from_numpy(scene).cuda(); d_calm = torch.from_numpy(CalM).cuda()
+                d_off = torch.tensor([0, Ns], dtype=torch.int64).cuda()
+                for n_hyp, cand, rounds in ((5, 16, 2), (1000, 16, 0), (1000, 16, 2)):
+                    kw = dict(seed=77, candidates=cand, lo_rounds=rounds)
+                    what = (method, score, Ns, n_hyp, rounds)
+                    lst = ctx.robust_pose_scenes(method, d_scene, d_off, d_calm, n_hyp, 4.0, ns_max=Ns, **kw)
+                    dev = ctx.robust_pose(method, d_scene, d_calm, n_hyp, 4.0, **kw)
+                    torch.cuda.synchronize()
+                    host = ctx.robust_pose(method, scene, CalM, n_hyp, 4.0, **kw)
+                    assert lst["status"].shape == (1,) and lst["mask"].shape == (Ns,)
+                    one = {k: (v if k == "mask" else v[0]) for k, v in lst.items()}
+                    _assert_same_result(dev, one, what + ("device",))
+                    _assert_same_result(host, one, what + ("host",))
+                    if Ns == n:
+                        assert int(dev["status"]) == 0 and int(dev["inliers"]) == Ns, what   # noise-free: the one sample there is has a pose
+                    if n_hyp == 5:
+                        assert int(dev["candidates"]) <= 5, what
+    finally:
+        ctx.set_score("count")
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("method", METHODS)
+def test_shared_calm_equals_a_copy_per_scene(method):
+    """S = 3 scenes of 40, 7 and 300 matches: the shared (9, 3) CalM (handed to the pose kernels as it is) gives bit for bit what (S, 9, 3) holding three
+    copies of it gives (one copy per hypothesis row), on the device and the host path."""
+    from tft_vs_fund_amd import api
+    ctx = _ctx()
+    scenes = [_small_scene(40, False), _small_scene(7, True), _small_scene(300, False)]
+    CalM = scenes[0][1]
+    assert all(np.array_equal(c, CalM) for _, c in scenes)                    # (generate_scene_batch: one calibration)
+    packed, off = api.pack_ragged([a for a, _ in scenes])
+    copies = np.ascontiguousarray(np.stack([CalM] * 3))
+    kw = dict(seed=5, candidates=8, lo_rounds=2)
+    keys = ("mask", "inliers", "hypothesis", "refits", "candidates", "status")
+    d = lambda a: torch.from_numpy(a).cuda()
+    shared = ctx.robust_pose_scenes(method, d(packed), d(off), d(CalM), 500, 4.0, ns_max=300, **kw)
+    per = ctx.robust_pose_scenes(method, d(packed), d(off), d(copies), 500, 4.0, ns_max=300, **kw)
+    torch.cuda.synchronize()
+    _assert_same_result(shared, per, (method, "device"), keys)
+    assert _np(shared["status"])[[0, 2]].tolist() == [0, 0]
+    assert int(_np(shared["status"])[1]) == (0 if api.ROBUST_METHODS[method] == 7 else api.ST_TOO_FEW)
+    h_shared = ctx.robust_pose_scenes(method, packed, off, CalM, 500, 4.0, **kw)
+    h_per = ctx.robust_pose_scenes(method, packed, off, copies, 500, 4.0, **kw)
+    _assert_same_result(h_shared, h_per, (method, "host"), keys)
+    _assert_same_result(h_shared, shared, (method, "host against device"), keys)

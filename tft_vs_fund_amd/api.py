@@ -869,99 +869,76 @@ class Context:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
             raise ValueError("unknown refine method %r" % (refine,))
-        if confidence is not None:
-            return self._robust_pose_adaptive(method, scene, calm, n_hyp, threshold, seed, n_sample, candidates, lo_rounds, refine, polish,
-                                              *_check_adaptive(confidence, first_round))
-        mid = METHOD_IDS[method]
-        ns = 0 if n_sample is None else int(n_sample)
-        args = (int(seed), int(n_hyp), ns, float(threshold), int(candidates), int(lo_rounds))
-        if isinstance(scene, np.ndarray):
-            sc = np.ascontiguousarray(scene, dtype=np.float64)
-            if sc.ndim != 2 or sc.shape[1] != 6:
-                raise ValueError("scene must be (Ns, 6)")
-            Ns = sc.shape[0]
-            calm_cm, _ = self._calm_cm_np(calm, 1)
-            Rt2 = np.empty(12); Rt3 = np.empty(12); T = np.empty(27)
-            mask = np.zeros(Ns, dtype=np.uint8); info = np.zeros(4, dtype=np.int32); st = np.zeros(1, dtype=np.int32)
-            ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
-            _check(self.lib, self.lib.tff_robust_pose_host(self.handle, mid, ptr(sc), Ns, ptr(calm_cm), *args, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask),
-                                                           ptr(info), ptr(st)), "tff_robust_pose_host")
-            out = dict(R_t_2=Rt2.reshape(4, 3).T, R_t_3=Rt3.reshape(4, 3).T, T=T.reshape(3, 3, 3).transpose(2, 1, 0), mask=mask,
-                       inliers=int(info[0]), hypothesis=int(info[1]), refits=int(info[2]), candidates=int(info[3]), status=int(st[0]))
-            if getattr(self, "_score", 0):
-                out["score"] = int(self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]) if out["status"] == 0 else -1
-            inl = sc[mask != 0]
-        else:
-            if not (scene.is_cuda and scene.dtype == torch.float64 and scene.is_contiguous() and scene.dim() == 2 and scene.shape[1] == 6):
-                raise ValueError("scene must be a contiguous float64 CUDA tensor of shape (Ns, 6)")
-            dev = scene.device
-            Ns = scene.shape[0]
-            if isinstance(calm, np.ndarray):
-                calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
-            if tuple(calm.shape) != (9, 3):
-                raise ValueError("CalM must be (9, 3)")
-            calm = calm.to(device=dev, dtype=torch.float64)
-            calm_cm = calm.t().contiguous().reshape(27)
-            Rt2 = torch.empty(12, dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
-            T = torch.empty(27, dtype=torch.float64, device=dev)
-            mask = torch.empty(Ns, dtype=torch.uint8, device=dev)
-            info = torch.empty(4, dtype=torch.int32, device=dev); st = torch.empty(1, dtype=torch.int32, device=dev)
-            self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            _check(self.lib, self.lib.tff_robust_pose_dev(self.handle, mid, self._p(scene), Ns, self._p(calm_cm), *args, self._p(Rt2), self._p(Rt3),
-                                                          self._p(T), self._p(mask), self._p(info), self._p(st)), "tff_robust_pose_dev")
-            out = dict(R_t_2=Rt2.reshape(4, 3).t(), R_t_3=Rt3.reshape(4, 3).t(), T=T.reshape(3, 3, 3).permute(2, 1, 0), mask=mask,
-                       inliers=info[0], hypothesis=info[1], refits=info[2], candidates=info[3], status=st[0])
-            if getattr(self, "_score", 0):                                   # one more count call on the returned pose; no pose (NaN): -1
-                sco = self.inlier_count(scene, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]
-                out["score"] = torch.where(st[0] == 0, sco, torch.full_like(sco, -1))
-            inl = scene[mask != 0].contiguous() if refine is not None else None   # (boolean indexing reads the count on the host)
-        if refine is not None:
-            r = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
-            out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
-                       status_refined=r["status"][0])
-        if polish:
-            if isinstance(scene, np.ndarray):
-                self._polish(out, calm, sc, np.array([0, Ns], dtype=np.int64), True)
-                out["iter_polished"] = int(out["iter_polished"]); out["status_polished"] = int(out["status_polished"])
-                out["repr_err_polished"] = float(out["repr_err_polished"])
-            else:
-                self._polish(out, calm, scene, torch.arange(2, dtype=torch.int64, device=dev) * Ns, True)   # [0, Ns], made on the device
-        return out
-
-    def _robust_pose_adaptive(self, method, scene, calm, n_hyp, threshold, seed, n_sample, candidates, lo_rounds, refine, polish, confidence, first_round):
-        """robust_pose with a confidence: the S = 1 scenes call, reshaped to the one-scene dict; refine and polish as robust_pose does them"""
+        adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
         host = isinstance(scene, np.ndarray)
         if host:
             sc = np.ascontiguousarray(scene, dtype=np.float64)
             if sc.ndim != 2 or sc.shape[1] != 6:
                 raise ValueError("scene must be (Ns, 6)")
-            Ns = sc.shape[0]
-            offsets = np.array([0, Ns], dtype=np.int64)
-            if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) != (9, 3):
-                raise ValueError("CalM must be (9, 3)")
+            if not isinstance(calm, torch.Tensor):
+                calm = np.asarray(calm, dtype=np.float64)
+            if tuple(calm.shape) == (1, 9, 3):                               # (the numpy form has always taken the batch-of-one CalM of pose_batch)
+                calm = calm[0]
         else:
             if not (scene.is_cuda and scene.dtype == torch.float64 and scene.is_contiguous() and scene.dim() == 2 and scene.shape[1] == 6):
                 raise ValueError("scene must be a contiguous float64 CUDA tensor of shape (Ns, 6)")
-            if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) != (9, 3):
-                raise ValueError("CalM must be (9, 3)")
-            sc = scene; Ns = scene.shape[0]
+            sc = scene
             if isinstance(calm, np.ndarray):
                 calm = torch.from_numpy(np.ascontiguousarray(calm, dtype=np.float64))
-            calm = calm.to(device=scene.device, dtype=torch.float64)
-            offsets = torch.arange(2, dtype=torch.int64, device=scene.device) * Ns      # [0, Ns], made on the device
-        r = self.robust_pose_scenes(method, sc, offsets, calm, n_hyp, threshold, seed=seed, n_sample=n_sample, candidates=candidates, lo_rounds=lo_rounds,
-                                    ns_max=Ns, confidence=confidence, first_round=first_round)
-        one = (lambda a: a[0].item()) if host else (lambda a: a[0])
-        out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
-                   refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
-        if "score" in r:
-            out["score"] = one(r["score"])
-        out["n_hyp_used"] = one(r["n_hyp_used"])
+        if tuple(calm.shape) != (9, 3):
+            raise ValueError("CalM must be (9, 3)")
+        Ns = sc.shape[0]
+        offsets = None
+        if not host:
+            dev = sc.device
+            calm = calm.to(device=dev, dtype=torch.float64)
+            if polish or adaptive:
+                offsets = torch.arange(2, dtype=torch.int64, device=dev) * Ns   # [0, Ns], made on the device
+        elif polish or adaptive:
+            offsets = np.array([0, Ns], dtype=np.int64)
+        if adaptive:                                                         # the S = 1 scenes call, reshaped to the one-scene dict
+            r = self.robust_pose_scenes(method, sc, offsets, calm, n_hyp, threshold, seed=seed, n_sample=n_sample, candidates=candidates,
+                                        lo_rounds=lo_rounds, ns_max=Ns, confidence=adaptive[0], first_round=adaptive[1])
+            one = (lambda a: a[0].item()) if host else (lambda a: a[0])
+            out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
+                       refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
+            if "score" in r:
+                out["score"] = one(r["score"])
+            out["n_hyp_used"] = one(r["n_hyp_used"])
+        else:
+            mid = METHOD_IDS[method]
+            args = (int(seed), int(n_hyp), 0 if n_sample is None else int(n_sample), float(threshold), int(candidates), int(lo_rounds))
+            if host:
+                calm_cm, _ = self._calm_cm_np(calm, 1)
+                Rt2 = np.empty(12); Rt3 = np.empty(12); T = np.empty(27)
+                mask = np.zeros(Ns, dtype=np.uint8); info = np.zeros(4, dtype=np.int32); st = np.zeros(1, dtype=np.int32)
+                ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+                _check(self.lib, self.lib.tff_robust_pose_host(self.handle, mid, ptr(sc), Ns, ptr(calm_cm), *args, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask),
+                                                               ptr(info), ptr(st)), "tff_robust_pose_host")
+                out = dict(R_t_2=Rt2.reshape(4, 3).T, R_t_3=Rt3.reshape(4, 3).T, T=T.reshape(3, 3, 3).transpose(2, 1, 0), mask=mask,
+                           inliers=int(info[0]), hypothesis=int(info[1]), refits=int(info[2]), candidates=int(info[3]), status=int(st[0]))
+                if getattr(self, "_score", 0):
+                    out["score"] = int(self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]) if out["status"] == 0 else -1
+            else:
+                calm_cm = calm.t().contiguous().reshape(27)
+                Rt2 = torch.empty(12, dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
+                T = torch.empty(27, dtype=torch.float64, device=dev)
+                mask = torch.empty(Ns, dtype=torch.uint8, device=dev)
+                info = torch.empty(4, dtype=torch.int32, device=dev); st = torch.empty(1, dtype=torch.int32, device=dev)
+                self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+                _check(self.lib, self.lib.tff_robust_pose_dev(self.handle, mid, self._p(sc), Ns, self._p(calm_cm), *args, self._p(Rt2), self._p(Rt3),
+                                                              self._p(T), self._p(mask), self._p(info), self._p(st)), "tff_robust_pose_dev")
+                out = dict(R_t_2=Rt2.reshape(4, 3).t(), R_t_3=Rt3.reshape(4, 3).t(), T=T.reshape(3, 3, 3).permute(2, 1, 0), mask=mask,
+                           inliers=info[0], hypothesis=info[1], refits=info[2], candidates=info[3], status=st[0])
+                if getattr(self, "_score", 0):                               # one more count call on the returned pose; no pose (NaN): -1
+                    sco = self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]
+                    out["score"] = torch.where(st[0] == 0, sco, torch.full_like(sco, -1))
+        # refine and polish, the same for both forms
         if refine is not None:                                               # (boolean indexing reads the count on the host)
-            inl = sc[r["mask"] != 0] if host else sc[r["mask"] != 0].contiguous()
-            f = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
-            out.update(R_t_2_refined=f["R_t_2"][0], R_t_3_refined=f["R_t_3"][0], T_refined=f["T"][0], iter_refined=f["iter"][0],
-                       status_refined=f["status"][0])
+            inl = sc[out["mask"] != 0] if host else sc[out["mask"] != 0].contiguous()
+            r = self.pose_batch(refine, inl.reshape(1, -1, 6), calm, reconst=False)
+            out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
+                       status_refined=r["status"][0])
         if polish:
             self._polish(out, calm, sc, offsets, True)
             if host:

@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(256) k_ba_ragged_classes(const BaRaggedPlan a)
     a.cls_list[c * a.B + atomicAdd(a.cls_count + c, 1)] = (int)b;
 }
 
-// one workgroup per item walks its range in tiles of BA_RAGGED_TILE, as k_robust_compact
+// one workgroup per item walks its range in tiles of BA_RAGGED_TILE, as k_scenes_compact
 __global__ void __launch_bounds__(BA_RAGGED_TILE) k_ba_ragged_compact(const BaRaggedPlan a) {
     __shared__ int wsum[BA_RAGGED_TILE / 64];
     const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);

@@ -75,7 +75,7 @@ struct tff_ctx {
     int stage = -1;
     DevBuf in, calm, out, idx, scratch_status, gh_rec, gh_topt, gh_init, spill, pre_rec, retry;
     DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
-    DevBuf robust_hyp, robust_counts, robust_cand;   // tff_robust_pose_*: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust)
+    DevBuf robust_hyp, robust_counts, robust_cand;   // the robust estimators, one scene or many: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust_scenes)
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
@@ -779,25 +779,16 @@ int launch_inlier_count(tff_ctx* c, const double* scene, int32_t Ns, const doubl
     if (grid * tff::INLIER_WG_WAVES > B) grid = (B + tff::INLIER_WG_WAVES - 1) / tff::INLIER_WG_WAVES;
     return launch(c, msac ? tff::k_inlier_count_staged_msac : tff::k_inlier_count_staged, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, staged, a);
 }
-// one wavefront per hypothesis (robust_kernel.h::k_inlier_mask); gate: see InlierMaskArgs
-int launch_inlier_mask(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B, double threshold,
-                       uint8_t* mask, int32_t* counts, const int32_t* gate) {
-    tff::InlierMaskArgs a{scene, calm, Rt2, Rt3, (long)B, Ns, threshold, mask, counts, gate};
-    return launch(c, tff::k_inlier_mask, tff::pose_grid(B), 64, 0, a);
-}
-int launch_sample_indices(tff_ctx* c, uint64_t seed, int64_t first, const unsigned long long* keys, int64_t B, int32_t n, int32_t Ns, int32_t* out) {
-    tff::SampleArgs a{(unsigned long long)seed, (long)first, keys, (long)B, n, Ns, out};
-    return launch(c, tff::k_sample_indices, (unsigned)((B + 255) / 256), 256, 0, a);
-}
 
-// ---- robust estimation (tff_robust_pose_*; kernels and the chunking in robust_kernel.h) ------------------------------------------------------------
+// ---- robust estimation (tff_robust_pose_*, tff_robust_pose_scenes_*; kernels and the chunking in robust_kernel.h, robust_scenes_kernel.h) ------------------
+// the arguments check_robust judges: those of the one-scene entry points (the six outputs for its null-pointer test only; the seed is carried along unread)
 struct RobustCall {
     int32_t method; const double* scene; int32_t Ns; const double* calm; uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold;
     int32_t n_cand; int32_t lo_rounds;
     double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
 };
 int32_t robust_min_sample(int32_t method) { return method == TFF_METHOD_LINEAR_F ? 8 : 7; }
-// argument checks shared by the two forms; n_sample = 0 becomes the method's minimum; *route: the method's ragged chain (the refit)
+// argument checks shared by every form; n_sample = 0 becomes the method's minimum; *route: the method's ragged chain (the refit)
 int check_robust(const tff_ctx* c, RobustCall* q, const RaggedRoute** route) {
     if (q->method != TFF_METHOD_LINEAR_TFT && q->method != TFF_METHOD_LINEAR_F)
         return fail(TFF_E_INVALID, "robust estimation: the method must be TFF_METHOD_LINEAR_TFT or TFF_METHOD_LINEAR_F");
@@ -814,79 +805,8 @@ int check_robust(const tff_ctx* c, RobustCall* q, const RaggedRoute** route) {
     return ragged_route(c, q->method, route);                                // the refit's refusals: TFF_OPT_ROWS = 0, TFF_OPT_KERNEL = 1
 }
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-// device pointers; the lock is held and the context's device current
-int launch_robust(tff_ctx* c, const RaggedRoute& route, const RobustCall& q) {
-    const Method& m = METHODS[q.method];
-    const int K = q.n_cand, Ns = q.Ns, n = q.n_sample;
-    const int64_t chunk = q.n_hyp < tff::ROBUST_CHUNK ? q.n_hyp : tff::ROBUST_CHUNK;
-    // workspaces.  One chunk of hypotheses: poses (51 doubles) | status | sample indices
-    TFF_TRY(c->robust_hyp.reserve(align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * sizeof(int32_t)) + (size_t)chunk * n * sizeof(int32_t)));
-    TFF_TRY(c->robust_counts.reserve((size_t)q.n_hyp * sizeof(int32_t)));
-    char* hp = (char*)c->robust_hyp.p;
-    double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
-    int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
-    int32_t* h_idx = (int32_t*)hp;
-    int32_t* counts = (int32_t*)c->robust_counts.p;
-    // the candidates: keys | poses | refits | offsets | seven int arrays of K | sample indices | masks | the packed refit batch
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    const size_t o_sel = carve((size_t)K * 8), o_pose = carve((size_t)K * 51 * 8), o_ref = carve((size_t)K * 51 * 8), o_off = carve((size_t)(K + 1) * 8),
-                 o_int = carve((size_t)K * 7 * 4), o_idx = carve((size_t)K * n * 4), o_mask = carve((size_t)K * Ns), o_pack = carve((size_t)K * Ns * 6 * 8);
-    TFF_TRY(c->robust_cand.reserve(off));
-    char* cp = (char*)c->robust_cand.p;
-    unsigned long long* sel = (unsigned long long*)(cp + o_sel);
-    int32_t* ints = (int32_t*)(cp + o_int);
-    tff::RobustState s{};
-    s.sel = sel; s.K = K; s.Ns = Ns;
-    s.cnt = ints; s.seed_idx = ints + K; s.nref = ints + 2 * K; s.status = ints + 3 * K; s.ref_status = ints + 4 * K; s.ref_cnt = ints + 5 * K;
-    int32_t* mask_cnt = ints + 6 * K;
-    s.mask_cnt = mask_cnt;
-    s.pose = (double*)(cp + o_pose); s.ref_pose = (double*)(cp + o_ref);
-    s.offsets = (long*)(cp + o_off);
-    uint8_t* masks = (uint8_t*)(cp + o_mask);
-    s.mask = masks;
-    s.scene = q.scene; s.packed = (double*)(cp + o_pack);
-    int32_t* c_idx = (int32_t*)(cp + o_idx);
 
-    auto sampled = [&](const int32_t* idx, int64_t B, double* pose, int32_t* status) {   // the method's *_pose_sampled_dev on device records [Rt2 | Rt3 | T]
-        PoseCall p{q.scene, q.calm, 0, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
-        p.sample_idx = idx; p.sample_ns = Ns;
-        return m.launch(c, p);
-    };
-    // 1. hypotheses and their counts, chunk by chunk
-    for (int64_t first = 0; first < q.n_hyp; first += chunk) {
-        const int64_t B = q.n_hyp - first < chunk ? q.n_hyp - first : chunk;
-        TFF_TRY(launch_sample_indices(c, q.seed, first, nullptr, B, n, Ns, h_idx));
-        TFF_TRY(sampled(h_idx, B, h_pose, h_status));
-        TFF_TRY(launch_inlier_count(c, q.scene, Ns, q.calm, h_pose, h_pose + B * 12, B, q.threshold, counts + first, nullptr));
-        TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{counts + first, h_status, (long)B}));
-    }
-    // 2. the K best successes in the order (count descending, index ascending), then their poses again from their indices
-    TFF_HIP(hipMemsetAsync(sel, 0, (size_t)K * 8, c->stream));
-    const long topk_blocks = (q.n_hyp + tff::ROBUST_TOPK_THREADS - 1) / tff::ROBUST_TOPK_THREADS;
-    for (int r = 0; r < K; ++r)
-        TFF_TRY(launch(c, tff::k_robust_topk, (unsigned)(topk_blocks < 1024 ? topk_blocks : 1024), tff::ROBUST_TOPK_THREADS, 0, tff::RobustTopkArgs{counts, (long)q.n_hyp, sel, r, K}));
-    TFF_TRY(launch_sample_indices(c, q.seed, 0, sel, K, n, Ns, c_idx));
-    TFF_TRY(sampled(c_idx, K, s.pose, s.status));
-    TFF_TRY(launch(c, tff::k_robust_seed, 1, 64, 0, s));
-    // 3. local optimisation, all candidates at once: masks -> packed inliers -> one ragged refit -> counts -> adopt
-    for (int round = 0; round < q.lo_rounds; ++round) {
-        TFF_TRY(launch_inlier_mask(c, q.scene, Ns, q.calm, s.pose, s.pose + K * 12, K, q.threshold, masks, mask_cnt, nullptr));
-        TFF_TRY(launch(c, tff::k_robust_offsets, 1, 64, 0, s));
-        TFF_TRY(launch(c, tff::k_robust_compact, (unsigned)K, tff::ROBUST_COMPACT_THREADS, 0, s));
-        PoseCall p{s.packed, q.calm, 0, K, Ns, s.ref_pose, s.ref_pose + K * 12, s.ref_pose + K * 24, nullptr, nullptr, s.ref_status, nullptr};
-        p.offsets = (const int64_t*)s.offsets;
-        TFF_TRY(launch_ragged(c, route, p));
-        TFF_TRY(launch_inlier_count(c, q.scene, Ns, q.calm, s.ref_pose, s.ref_pose + K * 12, K, q.threshold, s.ref_cnt, nullptr));
-        TFF_TRY(launch(c, tff::k_robust_adopt, (unsigned)K, 64, 0, s));
-    }
-    // 4. the winner and the mask of its pose (skipped, the mask staying zero, when there is none)
-    TFF_TRY(launch(c, tff::k_robust_finish, 1, 64, 0, tff::RobustFinishArgs{s, q.Rt2, q.Rt3, q.T, q.info, q.status}));
-    TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)Ns, c->stream));
-    return launch_inlier_mask(c, q.scene, Ns, q.calm, q.Rt2, q.Rt3, 1, q.threshold, q.mask, q.info, q.status);
-}
-
-// ---- robust estimation for a batch of scenes (tff_robust_pose_scenes_*, tff_inlier_count_scenes_dev; kernels in robust_scenes_kernel.h) -----------------
+// one call of the chain: S scenes (S = 1, offsets null, calm_stride 0, n_total = ns_max = Ns: tff_robust_pose_dev)
 struct RoundPlan;
 struct ScenesCall {
     int32_t method; const double* scenes; const int64_t* offsets; int64_t n_total; int32_t ns_max; int64_t S; const double* calm; int64_t calm_stride;
@@ -962,7 +882,9 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         }
     }
     const int64_t chunk = rows_max < tff::ROBUST_CHUNK ? rows_max : tff::ROBUST_CHUNK;
-    const size_t hyp_bytes = align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * 27 * sizeof(double)) +
+    // one CalM per scene: every row gets a copy of its scene's for the pose kernels (stride 27).  A shared CalM goes to them as it is (stride 0): no copy is carved or written
+    const size_t copies = q.calm_stride ? 27 * sizeof(double) : 0;
+    const size_t hyp_bytes = align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * copies) +
                              align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)chunk * n * sizeof(int32_t));
     // ... and behind it, for the adaptive call: the round's dense counts | best (S x 8) | live (S x 4)
     const size_t round_bytes = q.plan ? align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)S * 8) + align256((size_t)S * 4) : 0;
@@ -974,11 +896,11 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
     }
     if (q.n_total) TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
-    // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate | flags | the packed refit batch
+    // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate (per-scene CalM only) | flags | the packed refit batch
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
     const size_t o_sel = carve((size_t)C * 8), o_pose = carve((size_t)C * 51 * 8), o_ref = carve((size_t)C * 51 * 8), o_off = carve((size_t)(C + 1) * 8),
-                 o_int = carve((size_t)C * 7 * 4), o_idx = carve((size_t)C * n * 4), o_calm = carve((size_t)C * 27 * 8),
+                 o_int = carve((size_t)C * 7 * 4), o_idx = carve((size_t)C * n * 4), o_calm = carve((size_t)C * copies),
                  o_mask = carve((size_t)K * q.n_total), o_pack = carve((size_t)K * q.n_total * 6 * 8);
     TFF_TRY(c->robust_cand.reserve(off));
     char* cp = (char*)c->robust_cand.p;
@@ -987,7 +909,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     tff::ScenesState st{};
     tff::RobustState& s = st.s;
     st.q = set; st.K = K; st.cap = (long)K * q.n_total;
-    s.sel = sel; s.K = C; s.Ns = 0;
+    s.sel = sel; s.K = C;
     s.cnt = ints; s.seed_idx = ints + C; s.nref = ints + 2 * C; s.status = ints + 3 * C; s.ref_status = ints + 4 * C; s.ref_cnt = ints + 5 * C;
     int32_t* mask_cnt = ints + 6 * C;
     s.mask_cnt = mask_cnt;
@@ -995,28 +917,28 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     s.offsets = (long*)(cp + o_off);
     uint8_t* masks = (uint8_t*)(cp + o_mask);
     s.mask = masks;
-    s.scene = q.scenes; s.packed = (double*)(cp + o_pack);
+    s.packed = (double*)(cp + o_pack);
     int32_t* c_idx = (int32_t*)(cp + o_idx);
-    double* c_calm = (double*)(cp + o_calm);
+    double* c_calm = copies ? (double*)(cp + o_calm) : nullptr;
     const tff::ScenesFinishArgs fin{st, q.Rt2, q.Rt3, q.T, q.info, q.status};
     if (q.n_total == 0) {                                                    // no scene can be valid, and the pose kernels must not gather from an empty array
         if (q.plan) TFF_HIP(hipMemsetAsync(q.used, 0, (size_t)S * sizeof(int32_t), c->stream));
         return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
     }
 
-    // one chunk of hypotheses: poses (51 doubles) | CalM (27) | status | sample indices
+    // one chunk of hypotheses: poses (51 doubles) | CalM (27, per-scene CalM only) | status | sample indices
     TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
     TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
     char* hp = (char*)c->robust_hyp.p;
     double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
-    double* h_calm = (double*)hp;                hp += align256((size_t)chunk * 27 * sizeof(double));
+    double* h_calm = copies ? (double*)hp : nullptr;   hp += align256((size_t)chunk * copies);
     int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
     int32_t* h_idx = (int32_t*)hp;               hp += align256((size_t)chunk * n * sizeof(int32_t));
     int32_t* counts = (int32_t*)c->robust_counts.p;
 
-    // the method's *_pose_sampled_dev on the packed array: global indices, one CalM per row
+    // the method's *_pose_sampled_dev on the packed array: global indices, one CalM per row (`calm`) or the shared one
     auto sampled = [&](const int32_t* idx, const double* calm, int64_t B, double* pose, int32_t* status) {
-        PoseCall p{q.scenes, calm, 27, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
+        PoseCall p{q.scenes, calm ? calm : q.calm, q.calm_stride, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
         p.sample_idx = idx; p.sample_ns = (int32_t)q.n_total;
         return m.launch(c, p);
     };
@@ -1053,7 +975,14 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
                        tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
         TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
-        TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, q.n_hyp, q.threshold, counts + first));
+        // The one branch on the form of the call: without offsets (tff_robust_pose_dev: one valid scene [0, n_total), shared CalM) the hypotheses are counted
+        // by the one-scene launcher, whose one-wavefront-per-hypothesis route serves a few thousand hypotheses better than sixteen per workgroup.  Measured
+        // (DESIGN.md 3.4): 0.05 ms per 1 000-hypothesis call, and the 1 M-hypothesis LinearF call back under the bar it missed by 0.16 % without it.  The
+        // integers are those of k_inlier_count_scenes (count_if_inlier / score_if_inlier in both; tests/test_gpu_robust.py, test_gpu_score.py).
+        // tff_robust_pose_host arrives with the offsets {0, Ns} and takes the other route, on purpose: it is keyed on what the kernels are given, the call
+        // is dominated by its copies and its synchronisation, and a second key would be a second special case.  The refit counts always go the scenes route.
+        if (!q.offsets) TFF_TRY(launch_inlier_count(c, q.scenes, (int32_t)q.n_total, q.calm, h_pose, h_pose + B * 12, B, q.threshold, counts + first, nullptr));
+        else TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, q.n_hyp, q.threshold, counts + first));
         TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{counts + first, h_status, (long)B}));
     }
     // 2. per scene the K best successes, then their poses again from their indices
@@ -1076,7 +1005,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
                        tff::ScenesMaskArgs{set, s.pose, s.pose + C * 12, (long)C, (long)K, q.threshold, masks, mask_cnt, s.cnt, nullptr}));
         TFF_TRY(launch(c, tff::k_scenes_offsets, 1, tff::SCENES_SCAN_THREADS, 0, st));
         TFF_TRY(launch(c, tff::k_scenes_compact, (unsigned)C, tff::ROBUST_COMPACT_THREADS, 0, st));
-        PoseCall p{s.packed, c_calm, 27, C, q.ns_max, s.ref_pose, s.ref_pose + C * 12, s.ref_pose + C * 24, nullptr, nullptr, s.ref_status, nullptr};
+        PoseCall p{s.packed, c_calm ? c_calm : q.calm, q.calm_stride, C, q.ns_max, s.ref_pose, s.ref_pose + C * 12, s.ref_pose + C * 24, nullptr, nullptr, s.ref_status, nullptr};
         p.offsets = (const int64_t*)s.offsets;
         TFF_TRY(launch_ragged(c, route, p));
         TFF_TRY(launch_count_scenes(c, set, s.ref_pose, s.ref_pose + C * 12, 0, C, K, q.threshold, s.ref_cnt));
@@ -1279,7 +1208,9 @@ int tff_pose_batch_ragged_host(tff_ctx* c, int32_t method, const double* corresp
 int tff_sample_indices_dev(tff_ctx* c, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, int32_t* sample_idx) {
     TFF_ENTER(c);
     if (n < 1 || n > tff::ROBUST_MAX_SAMPLE || Ns < n || B < 0 || first < 0) return fail(TFF_E_INVALID, "sample_indices: need 1 <= n <= 16, Ns >= n, B >= 0, first >= 0");
-    return run_batch(c, B, sample_idx != nullptr, "null pointer", nullptr, [&] { return launch_sample_indices(c, seed, first, nullptr, B, n, Ns, sample_idx); });
+    return run_batch(c, B, sample_idx != nullptr, "null pointer", nullptr, [&] {
+        return launch(c, tff::k_sample_indices, (unsigned)((B + 255) / 256), 256, 0, tff::SampleArgs{(unsigned long long)seed, (long)first, (long)B, n, Ns, sample_idx});
+    });
 }
 
 int tff_inlier_mask_batch_dev(tff_ctx* c, const double* scene, int32_t Ns, const double* calm, const double* Rt2, const double* Rt3, int64_t B,
@@ -1287,9 +1218,13 @@ int tff_inlier_mask_batch_dev(tff_ctx* c, const double* scene, int32_t Ns, const
     TFF_ENTER(c);
     if (B < 0 || Ns < 0) return fail(TFF_E_INVALID, "negative size");
     return run_batch(c, B, scene && calm && Rt2 && Rt3 && mask, "null pointer", nullptr,
-                     [&] { return launch_inlier_mask(c, scene, Ns, calm, Rt2, Rt3, B, threshold, mask, counts, nullptr); });
+                     [&] {                                                   // one wavefront per hypothesis
+                         return launch(c, tff::k_inlier_mask, tff::pose_grid(B), 64, 0, tff::InlierMaskArgs{scene, calm, Rt2, Rt3, (long)B, Ns, threshold, mask, counts});
+                     });
 }
 
+// The one-scene forms: their own refusals (check_robust with the real Ns: a scene smaller than a sample is TFF_E_INVALID here, not a per-scene status),
+// then the chain for S = 1.  The _dev form is given no offsets: a null SceneSet::offsets is the one scene [0, Ns)
 int tff_robust_pose_dev(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
                         int32_t* status) {
@@ -1298,38 +1233,8 @@ int tff_robust_pose_dev(tff_ctx* c, int32_t method, const double* scene, int32_t
     const RaggedRoute* route;
     TFF_TRY(check_robust(c, &q, &route));
     TFF_HIP(hipSetDevice(c->device));
-    return launch_robust(c, *route, q);
-}
-
-// host pointers: H2D of the scene and CalM, the _dev path, D2H of the outputs, one synchronisation
-int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
-                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
-                         int32_t* status) {
-    TFF_ENTER(c);
-    RobustCall h{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_robust(c, &h, &route));
-    TFF_HIP(hipSetDevice(c->device));
-    const size_t nscene = (size_t)Ns * 6 * sizeof(double);
-    TFF_TRY(c->in.reserve(nscene));
-    TFF_TRY(c->calm.reserve(27 * sizeof(double)));
-    TFF_TRY(c->out.reserve(51 * sizeof(double) + (size_t)Ns));
-    TFF_TRY(c->idx.reserve(5 * sizeof(int32_t)));
-    RobustCall d = h;
-    d.scene = (const double*)c->in.p; d.calm = (const double*)c->calm.p;
-    d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + 12; d.T = d.Rt3 + 12; d.mask = (uint8_t*)(d.T + 27);
-    d.info = (int32_t*)c->idx.p; d.status = d.info + 4;
-    TFF_HIP(hipMemcpyAsync(c->in.p, scene, nscene, hipMemcpyHostToDevice, c->stream));
-    TFF_HIP(hipMemcpyAsync(c->calm.p, calm, 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    TFF_TRY(launch_robust(c, *route, d));
-    TFF_HIP(hipMemcpyAsync(Rt2, d.Rt2, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(Rt3, d.Rt3, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(T, d.T, 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(mask, d.mask, (size_t)Ns, hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(info, d.info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(status, d.status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return launch_robust_scenes(c, *route, ScenesCall{method, scene, nullptr, Ns, Ns, 1, calm, 0, seed, n_hyp, q.n_sample, threshold, n_cand, lo_rounds,
+                                                      Rt2, Rt3, T, mask, info, status});
 }
 
 int tff_robust_pose_scenes_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max, int64_t S,
@@ -1397,6 +1302,17 @@ static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, 
     if (confidence) TFF_HIP(hipMemcpyAsync(used, d.used, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipStreamSynchronize(c->stream));
     return 0;
+}
+int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
+                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
+                         int32_t* status) {
+    TFF_ENTER(c);
+    RobustCall h{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_robust(c, &h, &route));
+    const int64_t offsets[2] = {0, Ns};
+    return robust_scenes_host(c, method, scene, offsets, 1, calm, 0, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status,
+                              nullptr, 0, nullptr);
 }
 int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                                 int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,

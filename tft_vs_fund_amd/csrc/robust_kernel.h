@@ -1,17 +1,18 @@
-// Robust three-view pose estimation (tff_robust_pose_*, tff_sample_indices_dev, tff_inlier_mask_batch_dev): RANSAC over minimal samples of one
-// scene with local optimisation of the K best hypotheses.  The hypotheses, their inlier counts and the refits come from the existing kernels
-// (the *_sampled route of the pose kernels, k_inlier_count_*, the ragged chain); this file holds what ties them together on the device:
+// Robust three-view pose estimation, the pieces that know nothing of scenes (tff_sample_indices_dev, tff_inlier_mask_batch_dev and the selection of
+// tff_robust_pose_*): RANSAC over minimal samples with local optimisation of the K best hypotheses.  The estimator itself is ONE chain of launches for
+// S scenes (robust_scenes_kernel.h); tff_robust_pose_* is its S = 1 form.  The hypotheses, their inlier counts and the refits come from the existing
+// kernels (the *_sampled route of the pose kernels, k_inlier_count_scenes -- for the hypotheses of tff_robust_pose_dev the one-scene count kernels of
+// blocks_kernel.h, same integers -- and the ragged chain); this file holds:
 //
-//   k_sample_indices   n distinct indices per hypothesis, a function of (seed, hypothesis index, n, Ns) alone (counter-based)
-//   k_inlier_mask      the inlier rule of k_repr_error per correspondence, written out as 0 / 1 flags (+ the row sums)
+//   k_sample_indices   n distinct indices per hypothesis, a function of (seed, hypothesis index, n, Ns) alone (counter-based): tff_sample_indices_dev
+//   k_inlier_mask      the inlier rule of k_repr_error per correspondence, written out as 0 / 1 flags (+ the row sums): tff_inlier_mask_batch_dev
 //   k_robust_mark      a failed hypothesis (status != 0) gets the count -1: it is never a candidate
 //   k_robust_topk      one round of the top-K selection: the largest packed key (count, index) below the previous round's
 //   k_robust_seed      the K keys -> candidate counts, hypothesis indices, validity
-//   k_robust_offsets   the candidates' inlier counts -> offsets of the packed refit batch
-//   k_robust_compact   a candidate's inliers, in scene order, into its range of the packed batch
 //   k_robust_adopt     a candidate takes its refit iff that succeeded and has at least as many inliers
-//   k_robust_finish    the winner (largest count, ties to the earlier candidate) -> the caller's outputs
 //
+// The two public kernels are the definition the estimator is pinned against (tests/test_gpu_robust.py): sample_draw and count_if_inlier are what the
+// chain's own k_scenes_sample and k_scenes_mask call.
 // Hypotheses are processed in chunks of ROBUST_CHUNK (the pose records of a chunk, 51 doubles per hypothesis, are the only workspace that grows
 // with the chunk: 107 MB); only the int32 counts of ALL hypotheses are kept, and the K winners are recomputed from their indices -- the sampler is
 // counter-based and a sampled hypothesis has the same bits in a batch of any size, so the result does not depend on the chunk size.
@@ -37,8 +38,7 @@ __device__ __forceinline__ int robust_key_count(unsigned long long key) { return
 
 struct SampleArgs {
     unsigned long long seed;
-    long first;                              // row b is hypothesis first + b ...
-    const unsigned long long* keys;          // ... or, when non-null, the hypothesis of selection key keys[b]
+    long first;                              // row b is hypothesis first + b
     long B;
     int n, Ns;                               // 1 <= n <= ROBUST_MAX_SAMPLE, Ns >= n
     int* out;                                // B x n
@@ -68,8 +68,7 @@ __device__ __forceinline__ void sample_draw(const unsigned long long seed, const
 __global__ void __launch_bounds__(256) k_sample_indices(const SampleArgs a) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
-    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(a.first + b);
-    sample_draw(a.seed, h, a.n, a.Ns, 0, a.out + b * a.n);
+    sample_draw(a.seed, (unsigned long long)(a.first + b), a.n, a.Ns, 0, a.out + b * a.n);
 }
 
 // ---- per-correspondence inlier flags ------------------------------------------------------------------------------------------------------------
@@ -82,13 +81,11 @@ struct InlierMaskArgs {
     double thr;
     unsigned char* mask;     // B x Ns
     int* counts;             // B or null: the row sums
-    const int* gate;         // null, or one int32: the kernel does nothing unless *gate == 0 (the estimator's status)
 };
 // One wavefront per hypothesis, the cameras composed and pinned as in k_repr_error, the rule per correspondence that of the count kernels
 // (count_if_inlier): the row sums are their counts.
 __global__ void __launch_bounds__(64, 4) k_inlier_mask(const InlierMaskArgs a) {
     __shared__ double cam[3][12];
-    if (a.gate && *a.gate != 0) return;
     const int lane = lane_id();
     for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
         wave_sync();
@@ -131,7 +128,7 @@ __global__ void __launch_bounds__(256) k_robust_mark(const RobustMarkArgs a) {
 
 // The order of the candidates is (count descending, hypothesis index ascending) = descending key (count + 1) << 32 | (2^32 - 1 - index); keys are
 // distinct, so round r takes the largest key below the one round r - 1 took and nothing has to be marked.  A key of 0 = nothing left.
-// blockIdx.y is the scene (one for tff_robust_pose_*): its counts at counts + y * n_hyp, its keys at sel + y * K, the keys built from h within the scene.
+// blockIdx.y is the scene: its counts at counts + y * n_hyp, its keys at sel + y * K, the keys built from h within the scene.
 struct RobustTopkArgs {
     const int* counts;       // n_hyp per scene, -1 = failed
     long n_hyp;
@@ -167,11 +164,10 @@ __global__ void __launch_bounds__(ROBUST_TOPK_THREADS) k_robust_topk(const Robus
     }
 }
 
-// The state of the K candidates, all device-resident
+// The state of the K candidates (K per scene x S scenes, robust_scenes_kernel.h::ScenesState), all device-resident
 struct RobustState {
     const unsigned long long* sel;   // K selection keys
     long K;
-    int Ns;
     int* cnt;                // K current inlier counts, -1 = no such candidate
     int* seed_idx;           // K hypothesis indices
     int* nref;               // K refits adopted
@@ -180,16 +176,15 @@ struct RobustState {
     double* ref_pose;        // K x 51, the refits, same layout
     int* ref_status;         // K
     int* ref_cnt;            // K
-    const unsigned char* mask;   // K x Ns
+    const unsigned char* mask;   // the candidates' inlier flags, packed per scene (ScenesMaskArgs)
     const int* mask_cnt;     // K row sums
     long* offsets;           // K + 1
-    const double* scene;
     double* packed;          // the refit batch
 };
-// runs after the candidates' hypotheses were recomputed from their keys (k_sample_indices with `keys`, the *_sampled pose kernels).  A candidate
+// runs after the candidates' hypotheses were recomputed from their keys (k_scenes_sample with `keys`, the *_sampled pose kernels).  A candidate
 // whose recomputed hypothesis is not a success cannot exist -- it was selected among the successes -- the test of its status is a guard
 __global__ void __launch_bounds__(64) k_robust_seed(const RobustState s) {
-    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;              // (one workgroup for K <= 64; S * K candidates: robust_scenes_kernel.h)
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= s.K) return;
     const unsigned long long key = s.sel[r];
     const bool valid = key != 0 && s.status[r] == 0;
@@ -197,48 +192,8 @@ __global__ void __launch_bounds__(64) k_robust_seed(const RobustState s) {
     s.seed_idx[r] = valid ? (int)robust_key_index(key) : -1;
     s.nref[r] = 0;
 }
-// offsets[r + 1] = offsets[r] + (inliers of candidate r, 0 where there is no candidate): K <= 64, one thread
-__global__ void __launch_bounds__(64) k_robust_offsets(const RobustState s) {
-    if (threadIdx.x != 0) return;
-    long o = 0;
-    s.offsets[0] = 0;
-    for (int r = 0; r < s.K; ++r) {
-        o += (s.cnt[r] >= 0) ? s.mask_cnt[r] : 0;
-        s.offsets[r + 1] = o;
-    }
-}
-// one workgroup per candidate walks the scene in tiles of 256: ballot + prefix over the four wavefronts keep the inliers in scene order
-constexpr int ROBUST_COMPACT_THREADS = 256;
-__global__ void __launch_bounds__(ROBUST_COMPACT_THREADS) k_robust_compact(const RobustState s) {
-    __shared__ int wsum[ROBUST_COMPACT_THREADS / 64];
-    const int r = (int)blockIdx.x;
-    if (s.cnt[r] < 0) return;
-    const unsigned char* m = s.mask + (long)r * s.Ns;
-    const long end = s.offsets[r + 1];
-    long base = s.offsets[r];
-    const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
-    for (int i0 = 0; i0 < s.Ns; i0 += ROBUST_COMPACT_THREADS) {
-        const int i = i0 + (int)threadIdx.x;
-        const bool in = i < s.Ns && m[i] != 0;
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) wsum[w] = __popcll(bal);
-        __syncthreads();
-        int before = __popcll(bal & ((1ULL << lane) - 1ULL)), total = 0;
-#pragma unroll
-        for (int k = 0; k < ROBUST_COMPACT_THREADS / 64; ++k) { before += (k < w) ? wsum[k] : 0; total += wsum[k]; }
-        const long slot = base + before;
-        if (in && slot < end) {                                              // (slot < end always holds: the offsets are this mask's row sums)
-            const double* q = s.scene + 6 * (long)i;
-            double* d = s.packed + 6 * slot;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) d[e] = q[e];
-        }
-        base += total;
-        __syncthreads();
-    }
-}
 __global__ void __launch_bounds__(64) k_robust_adopt(const RobustState s) {
-    const long r = (long)blockIdx.x;                                        // (long: S * K candidates index these arrays too, robust_scenes_kernel.h)
+    const long r = (long)blockIdx.x;                                        // (long: S * K candidates index these arrays)
     const int lane = (int)threadIdx.x;
     if (s.cnt[r] < 0 || s.ref_status[r] != 0 || s.ref_cnt[r] < s.cnt[r]) return;
     const long K = s.K;
@@ -246,34 +201,6 @@ __global__ void __launch_bounds__(64) k_robust_adopt(const RobustState s) {
     if (lane < 27) s.pose[K * 24 + r * 27 + lane] = s.ref_pose[K * 24 + r * 27 + lane];
     __syncthreads();                                                         // (the count is read above by every lane before lane 0 replaces it)
     if (lane == 0) { s.cnt[r] = s.ref_cnt[r]; s.nref[r] += 1; }
-}
-struct RobustFinishArgs {
-    RobustState s;
-    double* Rt2; double* Rt3; double* T;     // 12, 12, 27
-    int* info;               // 4
-    int* status;             // 1
-};
-__global__ void __launch_bounds__(64) k_robust_finish(const RobustFinishArgs a) {
-    const int lane = (int)threadIdx.x, K = (int)a.s.K;
-    int win = -1, best = -1, ncand = 0;
-    for (int r = 0; r < K; ++r) {
-        const int c = a.s.cnt[r];
-        if (c >= 0) ++ncand;
-        if (c > best) { best = c; win = r; }
-    }
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    if (lane < 12) {
-        a.Rt2[lane] = win >= 0 ? a.s.pose[win * 12 + lane] : qnan;
-        a.Rt3[lane] = win >= 0 ? a.s.pose[(K + win) * 12 + lane] : qnan;
-    }
-    if (lane < 27) a.T[lane] = win >= 0 ? a.s.pose[K * 24 + win * 27 + lane] : qnan;
-    if (lane == 0) {
-        a.info[0] = win >= 0 ? best : 0;
-        a.info[1] = win >= 0 ? a.s.seed_idx[win] : -1;
-        a.info[2] = win >= 0 ? a.s.nref[win] : 0;
-        a.info[3] = ncand;
-        a.status[0] = win >= 0 ? ST_OK : ST_NO_POSE;
-    }
 }
 
 }  // namespace tff

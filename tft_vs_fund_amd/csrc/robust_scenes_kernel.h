@@ -1,18 +1,18 @@
-// Robust pose estimation for a batch of scenes in one call (tff_robust_pose_scenes_*, tff_inlier_count_scenes_dev): the hypotheses of S scenes share
-// ONE chain of launches.  Scene s owns the correspondences offsets[s] .. offsets[s + 1] - 1 of a packed array; hypothesis g = s * n_hyp + h is
-// hypothesis h of scene s, and everything it computes is what tff_robust_pose_dev computes for that scene alone with seed + s: the sampler is
-// counter-based, the unchanged *_sampled pose kernels gather GLOBAL indices from the packed array, the per-match inlier rule is count_if_inlier, the
-// refit is the ragged chain over the S * K candidates.  This file holds the glue:
+// The robust pose estimator (tff_robust_pose_*, tff_robust_pose_scenes_*, tff_inlier_count_scenes_dev): the hypotheses of S scenes share ONE chain of
+// launches, and the one-scene call is that chain with S = 1.  Scene s owns the correspondences offsets[s] .. offsets[s + 1] - 1 of a packed array;
+// hypothesis g = s * n_hyp + h is hypothesis h of scene s, drawn with seed + s, and nothing it computes depends on the other scenes: the sampler is
+// counter-based (robust_kernel.h::sample_draw), the unchanged *_sampled pose kernels gather GLOBAL indices from the packed array, the per-match inlier
+// rule is count_if_inlier, the refit is the ragged chain over the S * K candidates.  This file holds the glue:
 //
-//   k_scenes_sample        k_sample_indices per scene: global indices (-1 for an invalid scene) + the hypothesis's own copy of its scene's CalM
+//   k_scenes_sample        sample_draw per scene: global indices (-1 for an invalid scene) + with one CalM per scene the hypothesis's own copy of it
 //   k_inlier_count_scenes  the hot kernel: four hypotheses per wavefront, a workgroup serves one scene at a time (staged in LDS when it fits)
-//   k_scenes_mask          k_inlier_mask with a scene lookup; rows of different lengths, packed
+//   k_scenes_mask          the inlier flags of one pose per item, rows of different lengths, packed; the row sums are k_inlier_count_scenes's counts
 //   k_scenes_offsets       offsets of the S * K + 1 packed refit items: a one-workgroup scan
-//   k_scenes_compact       k_robust_compact with a scene lookup
-//   k_scenes_finish        k_robust_finish per scene, and the outputs of an invalid scene
+//   k_scenes_compact       a candidate's inliers, in scene order, into its range of the packed refit batch
+//   k_scenes_finish        per scene the winner (largest count, ties to the earlier candidate) -> the caller's outputs; the outputs of an invalid scene
 //   k_round_init / k_round_scatter / k_round_close   the adaptive call (tff_robust_pose_scenes_adaptive_*): rounds of hypotheses and the stop rule
 //
-// k_robust_mark, k_robust_topk (gridDim.y = S), k_robust_seed and k_robust_adopt (robust_kernel.h) serve both paths.  A chunk of ROBUST_CHUNK
+// k_robust_mark, k_robust_topk (gridDim.y = S), k_robust_seed and k_robust_adopt (robust_kernel.h) do the selection.  A chunk of ROBUST_CHUNK
 // hypotheses may cut a scene anywhere: every kernel derives (s, h) from g.
 #pragma once
 #include "robust_kernel.h"
@@ -22,7 +22,7 @@ namespace tff {
 
 struct SceneSet {
     const double* scenes;    // packed 6 x n_total
-    const long* offsets;     // S + 1, on the device
+    const long* offsets;     // S + 1, on the device; null (tff_robust_pose_dev, which is given none): S = 1 and the scene is [0, n_total)
     long S;
     long n_total;            // every offset lies in [0, n_total]
     int ns_max;              // a scene with more correspondences is ST_BAD_OFFSETS
@@ -32,7 +32,7 @@ struct SceneSet {
 };
 // the status of scene s and, when it is ST_OK, its range [*o, *o + *n) of the packed arrays: nothing else is ever used as an address
 __device__ __forceinline__ int scene_range(const SceneSet& q, const long s, long* o, int* n) {
-    const long o0 = q.offsets[s], o1 = q.offsets[s + 1];
+    const long o0 = q.offsets ? q.offsets[s] : 0, o1 = q.offsets ? q.offsets[s + 1] : q.n_total;
     *o = 0; *n = 0;
     if (o0 < 0 || o1 < o0 || o1 > q.n_total || o1 - o0 > (long)q.ns_max) return ST_BAD_OFFSETS;
     if (o1 - o0 < (long)q.n_min) return ST_TOO_FEW;
@@ -50,7 +50,7 @@ struct ScenesSampleArgs {
     long per;                // n_hyp, or K with `keys`
     int n;
     int* out;                // B x n indices into the packed array, -1 for an invalid scene
-    double* calm_out;        // B x 27: the row's CalM, for the pose kernels (calm_stride 27)
+    double* calm_out;        // B x 27: the row's CalM, for the pose kernels (calm_stride 27); null with a shared CalM, which they read themselves
     long hyp_base;           // a round of the adaptive call (per = the round's length): the row's hypothesis is hyp_base + g % per; 0 otherwise
     const int* live;         // null, or S: a scene with live[s] == 0 gets indices -1, like an invalid one
 };
@@ -65,6 +65,7 @@ __global__ void __launch_bounds__(256) k_scenes_sample(const ScenesSampleArgs a)
     int* out = a.out + b * a.n;
     if (ok) sample_draw(a.seed + (unsigned long long)s, h, a.n, ns, (int)o, out);
     else for (int i = 0; i < a.n; ++i) out[i] = -1;
+    if (!a.calm_out) return;
     const double* calm = a.q.calm + s * a.q.calm_stride;
     for (int e = 0; e < 27; ++e) a.calm_out[b * 27 + e] = calm[e];
 }
@@ -234,7 +235,7 @@ struct ScenesMaskArgs {
     const int* alive;        // null, or B: nothing is done for an item with alive[r] < 0 (no such candidate)
     const int* gate;         // null, or S: nothing is done for a scene with gate[s] != 0 (the estimator's status)
 };
-// k_inlier_mask per item: one wavefront per hypothesis, the cameras composed and pinned the same way
+// robust_kernel.h::k_inlier_mask per item: one wavefront per hypothesis, the cameras composed and pinned the same way
 __global__ void __launch_bounds__(64, 4) k_scenes_mask(const ScenesMaskArgs a) {
     __shared__ double cam[3][12];
     const int lane = lane_id();
@@ -280,7 +281,7 @@ __global__ void __launch_bounds__(64, 4) k_scenes_mask(const ScenesMaskArgs a) {
 // ---- the candidates of all scenes: C = S * K of them, candidate r = scene r / K ------------------------------------------------------------------
 // The state is RobustState's with K = C (poses, refits and the int arrays are C long); these two fields say how the C candidates map to scenes.
 struct ScenesState {
-    RobustState s;           // s.K = C; s.Ns, s.scene unused; s.mask: the packed flags (K x n_s per scene, at K * offsets[s])
+    RobustState s;           // s.K = C; s.mask: the packed flags (K x n_s per scene, at K * offsets[s])
     SceneSet q;
     int K;                   // candidates per scene
     long cap;                // correspondences the packed refit batch holds (K * n_total: enough unless scenes overlap, which only malformed offsets do)
@@ -311,7 +312,8 @@ __global__ void __launch_bounds__(SCENES_SCAN_THREADS) k_scenes_offsets(const Sc
         a.s.offsets[r + 1] = o < a.cap ? o : a.cap;
     }
 }
-// one workgroup per candidate walks its scene in tiles of 256, as k_robust_compact
+// one workgroup per candidate walks its scene in tiles of 256: ballot + prefix over the four wavefronts keep the inliers in scene order
+constexpr int ROBUST_COMPACT_THREADS = 256;
 __global__ void __launch_bounds__(ROBUST_COMPACT_THREADS) k_scenes_compact(const ScenesState a) {
     __shared__ int wsum[ROBUST_COMPACT_THREADS / 64];
     const long r = (long)blockIdx.x;
@@ -350,7 +352,7 @@ struct ScenesFinishArgs {
     int* info;               // S x 4
     int* status;             // S
 };
-// one wavefront per scene: k_robust_finish over the scene's K candidates; an invalid scene reports its status and reads no candidate
+// one wavefront per scene: the winner among the scene's K candidates; an invalid scene reports its status and reads no candidate
 __global__ void __launch_bounds__(64) k_scenes_finish(const ScenesFinishArgs f) {
     const int lane = (int)threadIdx.x, K = f.a.K;
     const long sc = (long)blockIdx.x, C = f.a.s.K;
@@ -381,7 +383,7 @@ __global__ void __launch_bounds__(64) k_scenes_finish(const ScenesFinishArgs f) 
 }
 
 // TFF_OPT_SCORE = 1 only: k_scenes_finish put the winner's SCORE into info[0]; the row sums of the final k_scenes_mask launch (the number of set flags of
-// each returned mask, written for the scenes with status 0) take its place, as the gated k_inlier_mask launch does for tff_robust_pose_*
+// each returned mask, written for the scenes with status 0) take its place
 struct ScenesInfoArgs { const int* flags; const int* status; int* info; long S; };
 __global__ void __launch_bounds__(256) k_scenes_info(const ScenesInfoArgs a) {
     const long sc = (long)blockIdx.x * blockDim.x + threadIdx.x;
