@@ -153,7 +153,7 @@ __device__ __forceinline__ bool rows_linear_f_middle(RowLds* w, RowRt* rt, doubl
 }
 
 template <bool RAGGED>
-__device__ __forceinline__ void linear_f_pose_rows(const LinearTftArgs& a) {
+__device__ __forceinline__ void linear_f_pose_rows(const LinearTftArgs& a) {       // (a: the calling kernel's own parameter, see kernarg_again)
     TFF_DYNAMIC_LDS(double, smem);
     if (a.retry_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.retry_zero = 0;   // (the counter of the context's next call; this call's was zeroed during the previous one)
     const int p = lane_id() & 15, row = lane_id() >> 4;
@@ -165,7 +165,7 @@ __device__ __forceinline__ void linear_f_pose_rows(const LinearTftArgs& a) {
         int status;
         if (N < 8) {                                                         // linearF.m:35-37 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
-            rows_store_nan<RAGGED>(a, j, N);
+            rows_store_nan<RAGGED, true>(a, j, N);
         } else {
             {
                 double cen[6];
@@ -175,12 +175,14 @@ __device__ __forceinline__ void linear_f_pose_rows(const LinearTftArgs& a) {
             wave_sync();
             bool ok = rows_linear_f_middle(w, rt, w->t, w->pa, j.dbg);       // (w->t: F21, F31)
             rows_recover_prepare(w, rt);
-            status = rows_pose_tail<true, false, RAGGED>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<true, false, RAGGED, true>(a, w, rt, j, N, ok);   // (a is the calling kernel's own argument record)
         }
         if (p == 0 && j.valid) {
-            if (a.iter) a.iter[j.b] = 0;                                     // LinearFPoseEstimation.m:77
-            a.status[j.b] = status;
-            if (status == ST_RETRY && a.retry_list) a.retry_list[atomicAdd(a.retry_count, 1)] = (int)j.b;   // the list the exact kernel walks
+            const auto* al = kernarg_again(a);                               // (needed here only: not kept in scalar registers through the kernel)
+            int* const oiter = al->iter; int* const ostatus = al->status; int* const olist = al->retry_list;
+            if (oiter) oiter[j.b] = 0;                                       // LinearFPoseEstimation.m:77
+            ostatus[j.b] = status;
+            if (status == ST_RETRY && olist) olist[atomicAdd(al->retry_count, 1)] = (int)j.b;   // the list the exact kernel walks
         }
     }
 }

@@ -583,6 +583,19 @@ __device__ __attribute__((noinline)) int tri_vote_fast(PoseLds* w, const double*
 // instructions of the second candidate.  Same arithmetic per candidate as tri_vote_fast.  Returns tri_vote_fast's value for candidate 0 in
 // the low and for candidate 1 in the high 16 bits (|score| <= 2 N <= 2^14 is the caller's business: it falls back to two single passes beyond).
 struct VoteCam { double PB[12], R3[4]; };
+// K doubles (K even) from a 16-byte aligned address, two at a time.  From LDS these are ds_read_b128 with a 16-bit immediate offset off one base
+// register; single doubles pair up as ds_read2_b64, whose 8-bit offsets end at 2 040 bytes and cost an address addition per pair beyond that.
+typedef double Pair16 __attribute__((vector_size(16), may_alias));
+template <int K>
+__device__ __forceinline__ void load_pairs16(const double* src, double* dst) {
+    static_assert(K % 2 == 0, "whole pairs");
+    const Pair16* s = reinterpret_cast<const Pair16*>(src);
+#pragma unroll
+    for (int c = 0; c < K; c += 2) {
+        const Pair16 v = s[c / 2];
+        dst[c] = v[0]; dst[c + 1] = v[1];
+    }
+}
 // what vote_one knows about the 4 x 4 system when it is done: the Cholesky factor of S + delta I short of its last pivot (d4, unfloored) and the
 // inhomogeneous point z -- exactly the state of spd_min_eigvec<4> before its first iteration (dlt_from_vote goes on from there)
 struct VoteFactor { double L[4][3], inv[3], d4, z[3], pfloor; };
@@ -600,11 +613,13 @@ __device__ __forceinline__ void vote_one(const double (&SA)[6], const VoteCam& c
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             if (c > r) continue;
-            double v = b0[r] * b0[c] + b1[r] * b1[c];
+            // (a sum of two products has two fused forms and the compiler's pick between them follows how the operands reached it; the form is
+            // written out, so that the votes' points do not move in the last bit when the loads around them change)
+            double v = fma(b0[r], b0[c], b1[r] * b1[c]);
             if (r < 3) v += SA[r * (r + 1) / 2 + c];
             S[r][c] = v;
         }
-    const double S33 = b0[3] * b0[3] + b1[3] * b1[3];
+    const double S33 = fma(b0[3], b0[3], b1[3] * b1[3]);
     const double tr3 = S[0][0] + S[1][1] + S[2][2];
     const double delta = 1e-14 * (tr3 + S33), pfloor = 1e-3 * delta + 1e-300;
     double L[4][3], inv[3];
@@ -668,8 +683,12 @@ __device__ __forceinline__ bool dlt_from_vote(const VoteFactor& f, double (&X)[4
     inv[3] = rsqrt_pos(fmax(f.d4, f.pfloor));
     const double nn0 = 1.0 + (f.z[0] * f.z[0] + f.z[1] * f.z[1] + f.z[2] * f.z[2]);
     const double r0 = rsqrt(nn0);
-    const bool fin = nn0 <= 1e300;
-    X[0] = fin ? f.z[0] * r0 : 0.5; X[1] = fin ? f.z[1] * r0 : 0.5; X[2] = fin ? f.z[2] * r0 : 0.5; X[3] = fin ? r0 : 0.5;
+    X[0] = f.z[0] * r0; X[1] = f.z[1] * r0; X[2] = f.z[2] * r0; X[3] = r0;
+    if (wave_any(!(nn0 <= 1e300))) {                                         // a non-finite start (rare): the uniform vector, on the lanes concerned
+        const bool fin = nn0 <= 1e300;
+        X[0] = fin ? X[0] : 0.5; X[1] = fin ? X[1] : 0.5; X[2] = fin ? X[2] : 0.5; X[3] = fin ? X[3] : 0.5;
+        pin_value(X[0]);                                                     // (keeps the branch a branch: without it the selects are hoisted back onto the common path)
+    }
     bool conv;
     chol_invit<4>(L, inv, X, 40, &conv);
     return conv;

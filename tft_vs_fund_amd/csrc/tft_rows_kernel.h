@@ -20,6 +20,7 @@
 #pragma once
 #include "tft_kernel.h"
 #include "tft_moments_kernel.h"
+#include <rows_target.h>
 
 namespace tff {
 
@@ -34,15 +35,16 @@ struct RowRt {
     double mats[28];       // M1, inv(M2), inv(M3) of transform_TFT
     double Ein[18];        // E21, E31 (row-major)
     double cand[2][21];    // per call: R (9, row-major), Rp (9), t (3)
-    double P[4][12];       // candidate cameras K_v [R_c | t]
-    double candRt[4][12];  // candidate poses
-    double Rt[2][12];      // chosen poses, row-major 3x4
-    double Pfin[3][12];    // final cameras
+    // (read a camera at a time, two doubles per load: every camera starts on a 16-byte boundary)
+    alignas(16) double P[4][12];       // candidate cameras K_v [R_c | t]
+    alignas(16) double candRt[4][12];  // candidate poses
+    alignas(16) double Rt[2][12];      // chosen poses, row-major 3x4
+    alignas(16) double Pfin[3][12];    // final cameras
 };
 constexpr int ROW_OV_DOUBLES = 380;      // >= 27 * 26 / 2 + 1 (packed factor + the zero slot), >= 27 * 28 / 2 (R of the exact tier, rows_qr.h), >= sizeof(RowRt)
 static_assert(sizeof(RowRt) <= ROW_OV_DOUBLES * sizeof(double), "overlay");
-struct RowLds {
-    double mom[96];        // moment sums (tft_kernel.h)
+struct alignas(16) RowLds {
+    alignas(16) double mom[96];        // moment sums (tft_kernel.h)
     double nrm[9];
     double calm[27];
     double t[27];          // linearTFT's tensor (normalised frame)
@@ -50,8 +52,10 @@ struct RowLds {
     double Q[18];
     double tp[15];
     double pa[18];         // linearTFT's a (-> P2, P3 of the constrained solution), for the iterative methods' linear stage
-    double ov[ROW_OV_DOUBLES];   // overlay: packed Cholesky factor | slice null vectors | Gp | RowRt
+    alignas(16) double ov[ROW_OV_DOUBLES];   // overlay: packed Cholesky factor | slice null vectors | Gp | RowRt
 };
+static_assert(sizeof(RowLds) == (96 + 9 + 27 + 27 + 6 + 18 + 15 + 18 + ROW_OV_DOUBLES) * sizeof(double), "alignment adds no padding");
+static_assert(sizeof(RowRt) == 318 * sizeof(double) && alignof(RowRt) == 16, "alignment adds no padding");
 constexpr int ROW_LDS_DOUBLES = (int)(sizeof(RowLds) / sizeof(double));
 static_assert(ROW_LDS_DOUBLES % 2 == 0, "16-byte row stride");
 inline size_t rows_lds_bytes() { return (size_t)ROW_TRIPLETS * sizeof(RowLds); }
@@ -139,7 +143,7 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
         const double x2 = q.v[2] - c[2], y2 = q.v[3] - c[3];
         const double x3 = q.v[4] - c[4], y3 = q.v[5] - c[5];
         const double r1 = x1 * x1 + y1 * y1, r2 = x2 * x2 + y2 * y2, r3 = x3 * x3 + y3 * y3;
-        dA += sqrt_nonneg(odd ? r3 : r1);                                    // Normalize2Ddata.m:35
+        dA += sqrt_nonneg_uniform(odd ? r3 : r1);                            // Normalize2Ddata.m:35
         r2_out = r2;
         const double q2[4] = {1.0, x2, y2, r2};
         const double q3[4] = {1.0, x3, y3, r3};
@@ -168,7 +172,7 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
             if (i + 3 * STEP < N) po = rows_load(s, i + 3 * STEP);
             body(r, r2b);
         }
-        dB += sqrt_nonneg(odd ? r2b : r2a);
+        dB += sqrt_nonneg_uniform(odd ? r2b : r2a);
     }
     // mean distances -> scales and offsets (every lane of the row)
     const double d1 = row_sum16(odd ? 0.0 : dA), d3 = row_sum16(odd ? dA : 0.0), d2 = row_sum16(dB);
@@ -601,7 +605,7 @@ __device__ __forceinline__ bool rows_votes(const RowSrc& s, const int N, const R
 #pragma unroll
             for (int rr = 0; rr < 3; ++rr)
 #pragma unroll
-                for (int c = 0; c <= rr; ++c) SA[rr * (rr + 1) / 2 + c] = a0[rr] * a0[c] + a1[rr] * a1[c];
+                for (int c = 0; c <= rr; ++c) SA[rr * (rr + 1) / 2 + c] = fma(a0[rr], a0[c], a1[rr] * a1[c]);   // (the fused form written out: vote_one)
             const bool first = sweep == 0 && i0 == 0;
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
@@ -611,12 +615,8 @@ __device__ __forceinline__ bool rows_votes(const RowSrc& s, const int N, const R
                 if (evalA) {
                     VoteCam cam;
                     const int off = opaque_lane_int(offA[call]);
-                    const double* pb = rt->P[0] + off;
-                    const double* pr = rt->candRt[0] + off;
-#pragma unroll
-                    for (int c = 0; c < 12; ++c) cam.PB[c] = pb[c];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) cam.R3[c] = pr[8 + c];
+                    load_pairs16<12>(rt->P[0] + off, cam.PB);
+                    load_pairs16<4>(rt->candRt[0] + off + 8, cam.R3);
                     int term = 0;
                     bool cert = true;
                     // (view 2's main candidate past the first trip: its two signs come from the converged point of the scale sums below)
@@ -629,12 +629,8 @@ __device__ __forceinline__ bool rows_votes(const RowSrc& s, const int N, const R
                 if (evalB[call]) {
                     VoteCam cam;
                     const int off = opaque_lane_int(offB[call]);
-                    const double* pb = rt->P[0] + off;
-                    const double* pr = rt->candRt[0] + off;
-#pragma unroll
-                    for (int c = 0; c < 12; ++c) cam.PB[c] = pb[c];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) cam.R3[c] = pr[8 + c];
+                    load_pairs16<12>(rt->P[0] + off, cam.PB);
+                    load_pairs16<4>(rt->candRt[0] + off + 8, cam.R3);
                     int term = 0;
                     bool cert = true;
                     if (SPEC && call == 0 && first) vote_one<true>(SA, cam, x2, y2, term, cert, &fB);
@@ -665,15 +661,17 @@ __device__ __forceinline__ bool rows_votes(const RowSrc& s, const int N, const R
                     const bool conv = dlt_from_vote(fA, X);
                     sconv = sconv && (conv || !have);
                     if (!first) {                                            // the vote's exact tier (pose_common.h::tri_vote_exact): signs of the converged point
-                        const double* pr = rt->candRt[0] + opaque_lane_int(offA[0]);
+                        double pr[4];
+                        load_pairs16<4>(rt->candRt[0] + opaque_lane_int(offA[0]) + 8, pr);
                         const double s4 = sgn(X[3]);                         // X1 = X ./ X(4)
-                        const double d1 = X[2] * s4, d2 = (pr[8] * X[0] + pr[9] * X[1] + pr[10] * X[2] + pr[11] * X[3]) * s4;
+                        const double d1 = X[2] * s4, d2 = (pr[0] * X[0] + pr[1] * X[1] + pr[2] * X[2] + pr[3] * X[3]) * s4;
                         scA[0] += have ? sgn_i(d1) + sgn_i(d2) : 0;
                         certA[0] = certA[0] && (conv || !have);
                     }
                     const double iw = 1.0 / X[3];
                     const double X0 = X[0] * iw, X1 = X[1] * iw, X2 = X[2] * iw;
-                    const double* ax = rt->P[0] + opaque_lane_int(offA[1]);  // K3 [R3 | t3] of view 3's main candidate
+                    double ax[12];                                           // K3 [R3 | t3] of view 3's main candidate
+                    load_pairs16<12>(rt->P[0] + opaque_lane_int(offA[1]), ax);
                     double X3[3], u3[3];
 #pragma unroll
                     for (int r = 0; r < 3; ++r) { X3[r] = ax[4 * r] * X0 + ax[4 * r + 1] * X1 + ax[4 * r + 2] * X2; u3[r] = ax[4 * r + 3]; }
@@ -843,15 +841,24 @@ __device__ __forceinline__ RowJob rows_begin_ragged(const LinearTftArgs& a, RowL
     if (p < 11) w->calm[16 + p] = a.calm[j.b * a.calm_stride + 16 + p];
     return j;
 }
-template <bool RAGGED = false>
+// The argument record as a late user sees it.  KERNARG: `a` is the calling kernel's own (single, by-value) parameter, and the fields wanted here are
+// read again from the kernarg segment instead of being kept in scalar registers (or spilled to lanes) through everything that came before.
+template <bool KERNARG>
+__device__ __forceinline__ auto rows_args_at(const LinearTftArgs& a) {
+    if constexpr (KERNARG) return kernarg_again(a);
+    else return &a;
+}
+template <bool RAGGED = false, bool KERNARG = false>
 __device__ __forceinline__ void rows_store_nan(const LinearTftArgs& a, const RowJob& j, const int N) {
     const int p = rows_p();
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     if (j.valid) {
-        if (p < 12) { a.Rt2[j.b * 12 + p] = qnan; a.Rt3[j.b * 12 + p] = qnan; }
-        a.T[j.b * 27 + p] = qnan;
-        if (p < 11) a.T[j.b * 27 + 16 + p] = qnan;
-        if (a.reconst) for (int i = p; i < 3 * N; i += ROWL) a.reconst[(RAGGED ? 3 * j.base : j.b * 3 * (long)N) + i] = qnan;
+        const auto* al = rows_args_at<KERNARG>(a);
+        double* const oRt2 = al->Rt2; double* const oRt3 = al->Rt3; double* const oT = al->T; double* const orec = al->reconst;
+        if (p < 12) { oRt2[j.b * 12 + p] = qnan; oRt3[j.b * 12 + p] = qnan; }
+        oT[j.b * 27 + p] = qnan;
+        if (p < 11) oT[j.b * 27 + 16 + p] = qnan;
+        if (orec) for (int i = p; i < 3 * N; i += ROWL) orec[(RAGGED ? 3 * j.base : j.b * 3 * (long)N) + i] = qnan;
     }
 }
 
@@ -906,7 +913,8 @@ __device__ __forceinline__ void rows_vote_exact_pair(const RowSrc& s, const int 
 
 // EXACT: every score is evaluated (all four candidates), an uncertified one is recomputed by rows_vote_exact, the t3 scale and Reconst take the
 // certified DLT ladder -- the row then fails only on what the caller's exact tiers reported.
-template <bool T_FROM_CAMERAS, bool EXACT = false, bool RAGGED = false>
+// KERNARG: `a` is the calling kernel's own argument record; the output pointers are read again from it at the stores (kernarg_again).
+template <bool T_FROM_CAMERAS, bool EXACT = false, bool RAGGED = false, bool KERNARG = false>
 __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w, RowRt* rt, const RowJob& j, const int N, bool ok) {
     const int p = rows_p();
     double* dbg = j.dbg;
@@ -988,7 +996,8 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
         wave_sync();
     }
     rows_stamp(dbg, 12);
-    if (a.reconst || T_FROM_CAMERAS) {
+    double* const oreconst = rows_args_at<KERNARG>(a)->reconst;
+    if (oreconst || T_FROM_CAMERAS) {
         if (p == 0) compose_camera_from_pose(load_K(w->calm, 2), rt->Rt[1], rt->Pfin[2]);           // K3 [R3 | lam t3]
         wave_sync();
     }
@@ -1029,11 +1038,11 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
         bad = bad || !(fabs(vRt[h]) <= 1.79e308) || !(fabs(vT[h]) <= 1.79e308);
     }
     const bool nonfinite = row_any(bad);                                     // (the ballot is the whole wavefront's: outside every per-row branch)
-    if (a.reconst) {                                                         // LinearTFTPoseEstimation.m:59-60
+    if (oreconst) {                                                          // LinearTFTPoseEstimation.m:59-60
         double n0, d0;
         // only a row that owns a live triplet stores: a tail row, a failed triplet (its Reconst is NaN) and a row that is merely carried
         // along by a neighbour's exact-tier redo (k_gh_finish_rows) leave Reconst alone -- a triplet's bits never depend on its neighbours
-        double* rec = (j.valid && !j.bad_index && !nonfinite) ? a.reconst + (RAGGED ? 3 * j.base : b * 3 * (long)N) : nullptr;
+        double* rec = (j.valid && !j.bad_index && !nonfinite) ? oreconst + (RAGGED ? 3 * j.base : b * 3 * (long)N) : nullptr;
         const bool conv = rows_tri_pass<TRI_RECONST, EXACT>(j.src, N, rt->Pfin[0], rt->Pfin[1], rt->Pfin[2], rec, n0, d0);
         ok = ok && conv;
     }
@@ -1041,15 +1050,19 @@ __device__ __forceinline__ int rows_pose_tail(const LinearTftArgs& a, RowLds* w,
     else if (!ok) status = ST_RETRY;                                         // redone by the exact kernel
     else if (nonfinite && status == ST_OK) status = ST_NONFINITE;            // non-finite outputs -> status 2
     if (j.bad_index || (ok && nonfinite)) {
-        rows_store_nan<RAGGED>(a, j, N);                                     // (stores only for a row that owns a triplet)
+        rows_store_nan<RAGGED, KERNARG>(a, j, N);                            // (stores only for a row that owns a triplet)
     } else {
         const bool store = j.valid && ok;                                    // per row
+        auto stores = [&](const auto* al) {
+            double* const oRt2 = al->Rt2; double* const oRt3 = al->Rt3; double* const oT = al->T;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int e24 = 16 * h + p;
-            if (e24 < 24 && store) ((e24 >= 12) ? a.Rt3 : a.Rt2)[b * 12 + e24 % 12] = vRt[h];
-            if (e24 < 27 && store) a.T[b * 27 + e24] = vT[h];
-        }
+            for (int h = 0; h < 2; ++h) {
+                const int e24 = 16 * h + p;
+                if (e24 < 24 && store) ((e24 >= 12) ? oRt3 : oRt2)[b * 12 + e24 % 12] = vRt[h];
+                if (e24 < 27 && store) oT[b * 27 + e24] = vT[h];
+            }
+        };
+        stores(rows_args_at<KERNARG>(a));
     }
     rows_stamp(dbg, 13);
     return status;
@@ -1073,7 +1086,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows(const LinearTftA
         int status;
         if (N < 7) {                                                         // experiments.m:99 (wave-uniform: N is the batch's)
             status = ST_TOO_FEW;
-            rows_store_nan<RAGGED>(a, j, N);
+            rows_store_nan<RAGGED, true>(a, j, N);
         } else {
             if constexpr (PRE) {
                 rows_load_pre(a.pre, j.b, w->mom, w->nrm);
@@ -1094,12 +1107,14 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows(const LinearTftA
             rows_transform_tft_inverse(w->t, rt->T1, rt->mats, [w](int v) { return normal_matrix(w->nrm, v); });   // :53
             ok = rows_rt_prepare(w, rt, dbg) && ok;                          // :56
             rows_stamp(dbg, 10);
-            status = rows_pose_tail<false, false, RAGGED>(a, w, rt, j, N, ok);
+            status = rows_pose_tail<false, false, RAGGED, true>(a, w, rt, j, N, ok);
         }
         if (p == 0 && j.valid) {
-            if (a.iter) a.iter[j.b] = 0;                                     // :62
-            a.status[j.b] = status;
-            if (status == ST_RETRY && a.retry_list) a.retry_list[atomicAdd(a.retry_count, 1)] = (int)j.b;   // the list the exact kernel walks
+            const auto* al = kernarg_again(a);                               // (needed here only: not kept in scalar registers through the kernel)
+            int* const oiter = al->iter; int* const ostatus = al->status; int* const olist = al->retry_list;
+            if (oiter) oiter[j.b] = 0;                                       // :62
+            ostatus[j.b] = status;
+            if (status == ST_RETRY && olist) olist[atomicAdd(al->retry_count, 1)] = (int)j.b;   // the list the exact kernel walks
         }
     }
 }
