@@ -449,6 +449,10 @@ int tff_robust_pose_scenes_host(tff_ctx* ctx, int32_t method, const double* scen
  * call's: 4 bytes per row of a chunk and 12 S bytes. */
 /* Declared in tftfund_adaptive.h, which this header includes at its end: tff_robust_pose_scenes_adaptive_dev / _host (the arguments of
  * tff_robust_pose_scenes_*, plus `double confidence, int32_t first_round` after lo_rounds and `int32_t* used` before status) and tff_robust_round_plan. */
+/* Declared in tftfund_guided.h, included at the end as well: quality-guided (PROSAC) sampling.  tff_robust_pose_scenes_guided_dev / _host take the adaptive
+ * call's arguments plus `const int32_t* order, int64_t growth` after first_round: per scene a ranking of its correspondences, best first; the early
+ * hypotheses draw from the best-ranked ones, and after `growth` draws the sampling is the uniform one.  tff_sample_indices_guided_dev is the sampler alone.
+ * The definition and the refusals are stated in that header.  Without a ranking every call above computes what it always did. */
 
 /* Inlier counts of S * per_scene pose hypotheses, hypothesis b against scene b / per_scene with that scene's CalM: counts[b] is what
  * tff_inlier_count_batch_dev returns for that pose against that scene alone (the same rule per correspondence; the same scores at TFF_OPT_SCORE = 1).  The hypotheses of a scene whose offsets are
@@ -523,4 +527,5 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 }
 #endif
 #include "tftfund_adaptive.h"   /* entry points added after library version 103 */
+#include "tftfund_guided.h"     /* entry points added after library version 104 */
 #endif

@@ -129,13 +129,16 @@ def load_library(path=None):
             "tff_robust_pose_scenes_adaptive_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, V, V, V, V, V, V],
             "tff_robust_pose_scenes_adaptive_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, V, V, V, V, V, V],
             "tff_robust_round_plan": [F64, I64, I32, V, V, V],
+            "tff_robust_pose_scenes_guided_dev": [V, I32, V, V, I64, I32, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, I64, V, V, V, V, V, V, V],
+            "tff_robust_pose_scenes_guided_host": [V, I32, V, V, I64, V, I64, U64, I64, I32, F64, I32, I32, F64, I32, V, I64, V, V, V, V, V, V, V],
+            "tff_sample_indices_guided_dev": [V, U64, I64, I64, I32, I32, V, I64, V],
             "tff_bundle_adjust_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_class_bounds": [V],
             "tff_optim_f_ragged_bounds": [V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -185,6 +188,8 @@ EXPORTED_SYMBOLS = [
 # ... and every symbol include/tftfund_adaptive.h declares: the entry points added after library version 103, in the header that tftfund.h includes at
 # its end.  (EXPORTED_SYMBOLS is the ABI of version 103 and is pinned as such: tests/test_score_cpu.py, tests/test_capi_symbols.py.)
 ADAPTIVE_SYMBOLS = ["tff_robust_pose_scenes_adaptive_dev", "tff_robust_pose_scenes_adaptive_host", "tff_robust_round_plan"]
+# ... and every symbol include/tftfund_guided.h declares: the entry points added after library version 104 (quality-guided sampling)
+GUIDED_SYMBOLS = ["tff_robust_pose_scenes_guided_dev", "tff_robust_pose_scenes_guided_host", "tff_sample_indices_guided_dev"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -200,6 +205,8 @@ ROBUST_METHODS = {"LinearTFTPoseEstimation": 7, "LinearFPoseEstimation": 8}
 
 
 MAX_ROUNDS = 32              # rounds of the adaptive robust call (tff_robust_round_plan)
+GUIDED_MAX_GROWTH = 2 ** 31 - 2 ** 25   # the largest `growth` of the guided sampler: its pool table stays an int32 (include/tftfund_guided.h)
+GUIDED_MAX_N = 1 << 24       # ... for scenes of up to 2^24 correspondences, the bound of every robust call
 
 
 def _check_adaptive(confidence, first_round):
@@ -248,15 +255,14 @@ def _splitmix64(x):
     return z ^ (z >> np.uint64(31))
 
 
-def sample_indices_reference(seed, first, B, n, Ns):
-    """What tff_sample_indices_dev computes (include/tftfund.h), in numpy: (B, n) int32, row b = n distinct indices in [0, Ns), a function of
-    (seed, first + b, n, Ns) only.  A Fisher-Yates shuffle of the virtual array 0 .. Ns-1 of which only the n swaps are kept; wrapping uint64."""
-    if not (1 <= n <= 16 and Ns >= n and B >= 0 and first >= 0):
-        raise ValueError("need 1 <= n <= 16, Ns >= n, B >= 0, first >= 0")
+def _sample_rows(seed, h, n, Ns):
+    """the sampler of sample_indices_reference for rows with their own hypothesis index h (uint64) and their own Ns (a scalar or one per row): (len(h), n)
+    int64.  A Fisher-Yates shuffle of the virtual array 0 .. Ns-1 of which only the n swaps are kept; wrapping uint64."""
+    B = h.shape[0]
+    Ns = np.broadcast_to(np.asarray(Ns, dtype=np.int64), (B,))
     with np.errstate(over="ignore"):
-        h = np.uint64(first) + np.arange(B, dtype=np.uint64)
         key = _splitmix64(np.uint64(seed) ^ (h * np.uint64(0xD1342543DE82EF95)))
-        out = np.empty((B, n), dtype=np.int32)
+        out = np.empty((B, n), dtype=np.int64)
         pos = np.empty((B, n), dtype=np.int64)
         val = np.empty((B, n), dtype=np.int64)
 
@@ -268,12 +274,100 @@ def sample_indices_reference(seed, first, B, n, Ns):
 
         for i in range(n):
             u = _splitmix64(key + np.uint64(i)) >> np.uint64(32)
-            r = (np.uint64(i) + ((u * np.uint64(Ns - i)) >> np.uint64(32))).astype(np.int64)
+            r = (np.uint64(i) + ((u * (Ns - i).astype(np.uint64)) >> np.uint64(32))).astype(np.int64)
             vr, vi = look(r, i), look(np.full(B, i, dtype=np.int64), i)
             out[:, i] = vr
             pos[:, i] = r
             val[:, i] = vi
     return out
+
+
+def sample_indices_reference(seed, first, B, n, Ns):
+    """What tff_sample_indices_dev computes (include/tftfund.h), in numpy: (B, n) int32, row b = n distinct indices in [0, Ns), a function of
+    (seed, first + b, n, Ns) only.  A Fisher-Yates shuffle of the virtual array 0 .. Ns-1 of which only the n swaps are kept; wrapping uint64."""
+    if not (1 <= n <= 16 and Ns >= n and B >= 0 and first >= 0):
+        raise ValueError("need 1 <= n <= 16, Ns >= n, B >= 0, first >= 0")
+    with np.errstate(over="ignore"):
+        h = np.uint64(first) + np.arange(B, dtype=np.uint64)
+    return _sample_rows(seed, h, n, Ns).astype(np.int32)
+
+
+def _check_growth(growth):
+    """the growth of the guided sampler, refused as the library refuses it"""
+    g = int(growth)
+    if g != growth or not (1 <= g <= GUIDED_MAX_GROWTH):
+        raise ValueError("growth must be an integer between 1 and 2^31 - 2^25, not %r" % (growth,))
+    return g
+
+
+def guided_pool_ends(Ns, n, growth):
+    """The pool table of the guided (PROSAC) sampler for a scene of Ns correspondences and samples of n (include/tftfund_guided.h), in numpy: (Ns + 1,)
+    int32 with ends[k] = 0 below n, ends[n] = 1 and ends[k + 1] = ends[k] + ceil(T(k + 1) - T(k)), T(k) = growth * C(k, n) / C(Ns, n) evaluated in double
+    as growth * (k - i) / (Ns - i) over i = 0 .. n-1, multiply then divide.  The 1-based hypothesis t draws from the smallest pool k with ends[k] >= t,
+    uniformly beyond ends[Ns] (<= growth + Ns)."""
+    G = _check_growth(growth)
+    Ns, n = int(Ns), int(n)
+    if not (1 <= n <= 16 and n <= Ns <= GUIDED_MAX_N):
+        raise ValueError("need 1 <= n <= 16 and n <= Ns <= 2^24")
+    k = np.arange(n, Ns + 1, dtype=np.float64)
+    T = np.full(k.shape, np.float64(G))
+    for i in range(n):
+        T = T * (k - np.float64(i))
+        T = T / np.float64(Ns - i)
+    ends = np.zeros(Ns + 1, dtype=np.int64)
+    ends[n] = 1
+    ends[n + 1:] = 1 + np.cumsum(np.ceil(T[1:] - T[:-1]).astype(np.int64))
+    return ends.astype(np.int32)
+
+
+def guided_pool(ends, n, t):
+    """the pool of the 1-based hypotheses t (array) under the table `ends` of guided_pool_ends: the smallest k in [n, Ns] with ends[k] >= t, 0 where
+    t > ends[Ns] (the uniform draw)"""
+    t = np.asarray(t, dtype=np.uint64)
+    pool = n + np.searchsorted(ends[n:].astype(np.uint64), t, side="left")
+    return np.where(t > np.uint64(ends[-1]), 0, pool).astype(np.int64)
+
+
+def sample_indices_guided_reference(seed, first, B, n, order, growth):
+    """What tff_sample_indices_guided_dev computes (include/tftfund_guided.h), in numpy: (B, n) int32.  order (Ns,) is the scene's ranking, best first.
+    Hypothesis h = first + b with the pool k = guided_pool(ends, n, h + 1) draws the n - 1 ranks of the uniform sampler for (seed, h, n - 1, k - 1) and
+    then rank k - 1; without a pool the uniform sampler's ranks for (seed, h, n, Ns).  Row = order[ranks], or all -1 if one of those entries lies outside
+    [0, Ns)."""
+    order = np.asarray(order)
+    if order.ndim != 1 or not np.issubdtype(order.dtype, np.integer):
+        raise ValueError("order must be a 1-D integer array")
+    Ns = order.shape[0]
+    if not (B >= 0 and first >= 0):
+        raise ValueError("need B >= 0, first >= 0")
+    ends = guided_pool_ends(Ns, n, growth)
+    with np.errstate(over="ignore"):
+        h = np.uint64(first) + np.arange(B, dtype=np.uint64)
+        pool = guided_pool(ends, n, h + np.uint64(1))
+    ranks = np.empty((B, n), dtype=np.int64)
+    uni = pool == 0
+    ranks[uni] = _sample_rows(seed, h[uni], n, Ns)
+    if n > 1:
+        ranks[~uni, :n - 1] = _sample_rows(seed, h[~uni], n - 1, pool[~uni] - 1)
+    ranks[~uni, n - 1] = pool[~uni] - 1
+    idx = order.astype(np.int64)[ranks]
+    bad = ((idx < 0) | (idx >= Ns)).any(axis=1)
+    idx[bad] = -1
+    return idx.astype(np.int32)
+
+
+def order_from_quality(quality, offsets):
+    """The ranking the robust calls build from quality= on the host: quality (Ntot,) float, higher is better, NaN last; offsets (S + 1,) int64.  A stable
+    sort by descending quality, then a stable sort by scene, minus the scene's first offset: (Ntot,) int32, the ranking of scene s at offsets[s].  A packed
+    entry in front of offsets[0] or behind offsets[S] belongs to no scene: it keeps a slot outside every scene's range, which holds -1."""
+    q = np.asarray(quality, dtype=np.float64)
+    off = np.asarray(offsets, dtype=np.int64)
+    q = np.where(np.isnan(q), -np.inf, q)
+    by_q = np.argsort(-q, kind="stable")
+    S = off.shape[0] - 1
+    scene = np.searchsorted(off, np.arange(q.shape[0], dtype=np.int64), side="right") - 1     # -1 in front of offsets[0], S behind offsets[S]
+    glob = by_q[np.argsort(scene[by_q], kind="stable")]
+    sg = scene[glob]
+    return np.where((sg >= 0) & (sg < S), glob - off[np.clip(sg, 0, S)], -1).astype(np.int32)
 
 
 def pack_ragged(items):
@@ -840,6 +934,45 @@ class Context:
                "tff_sample_indices_dev")
         return out
 
+    def sample_indices_guided(self, seed, first, B, n, order, growth):
+        """tff_sample_indices_guided_dev: (B, n) int32 CUDA tensor, row b = the indices of hypothesis first + b under the guided (PROSAC) sampler for the
+        scene whose ranking, best first, is order (Ns,) int32 (see sample_indices_guided_reference)."""
+        g = _check_growth(growth)
+        self._begin()
+        order = self._t(order, torch.int32)
+        if order.dim() != 1:
+            raise ValueError("order must be (Ns,)")
+        out = torch.empty((max(int(B), 0), max(int(n), 0)), dtype=torch.int32, device=torch.device("cuda", self.device))
+        _check(self.lib, self.lib.tff_sample_indices_guided_dev(self.handle, int(seed), int(first), int(B), int(n), order.shape[0], self._p(order), g,
+                                                                self._p(out)), "tff_sample_indices_guided_dev")
+        return out
+
+    @staticmethod
+    def _check_guided(scenes, order, quality, growth):
+        """order= / quality= / growth= of robust_pose and robust_pose_scenes, judged before the library or a device is touched: None without a ranking,
+        else (the name given, the array, growth)"""
+        if order is None and quality is None:
+            return None
+        if order is not None and quality is not None:
+            raise ValueError("pass at most one of order and quality")
+        g = _check_growth(growth)
+        what, a = ("order", order) if order is not None else ("quality", quality)
+        if isinstance(scenes, np.ndarray):
+            if not isinstance(a, np.ndarray):
+                raise ValueError("%s must be a numpy array when the scenes are one (the host path)" % what)
+            integer, floating = np.issubdtype(a.dtype, np.integer) and a.dtype == np.int32, np.issubdtype(a.dtype, np.floating)
+        else:
+            if not (isinstance(a, torch.Tensor) and isinstance(scenes, torch.Tensor) and a.is_cuda and a.device == scenes.device):
+                raise ValueError("%s must be a CUDA tensor on the device of the scenes (the device path)" % what)
+            integer, floating = a.dtype == torch.int32, a.is_floating_point()
+        if a.ndim != 1 or a.shape[0] != scenes.shape[0]:
+            raise ValueError("%s must be (Ntot,): one entry per packed correspondence" % what)
+        if what == "order" and not integer:
+            raise ValueError("order must be int32")
+        if what == "quality" and not floating:
+            raise ValueError("quality must be a float array")
+        return what, a, g
+
     def inlier_mask(self, scene, calm, R_t_2, R_t_3, threshold, with_counts=False):
         """Inlier flags (B, Ns) uint8 of B pose hypotheses against one scene (Ns, 6), by the rule of inlier_count: the row sums are its counts."""
         self._begin()
@@ -853,7 +986,7 @@ class Context:
         return (mask, cnt) if with_counts else mask
 
     def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False,
-                    confidence=None, first_round=256):
+                    confidence=None, first_round=256, order=None, quality=None, growth=200000):
         """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
         best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
         Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
@@ -864,12 +997,15 @@ class Context:
         After set_score("msac") the hypotheses are ranked, refits adopted and the winner picked by the MSAC score, and `score` joins the dict: that of the
         returned pose, from one more inlier_count call (0-d CUDA tensor, no synchronisation / int; -1 without a pose).  mask and inliers stay the hard rule.
         confidence = c in (0, 1): the early stop of robust_pose_scenes for this one scene (the S = 1 call with the offsets [0, Ns]): n_hyp is the cap,
-        first_round the first round's length, and n_hyp_used joins the dict; the result is that of this call with n_hyp = n_hyp_used."""
+        first_round the first round's length, and n_hyp_used joins the dict; the result is that of this call with n_hyp = n_hyp_used.
+        order= (Ns,) int32, the matches best first, or quality= (Ns,) float, higher is better, with growth: the guided sampler of robust_pose_scenes for
+        this one scene (the S = 1 call with the offsets [0, Ns]); n_hyp_used joins the dict only with a confidence.  Without them nothing changes."""
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
             raise ValueError("unknown refine method %r" % (refine,))
         adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
+        guided = self._check_guided(scene, order, quality, growth)
         host = isinstance(scene, np.ndarray)
         if host:
             sc = np.ascontiguousarray(scene, dtype=np.float64)
@@ -892,19 +1028,21 @@ class Context:
         if not host:
             dev = sc.device
             calm = calm.to(device=dev, dtype=torch.float64)
-            if polish or adaptive:
+            if polish or adaptive or guided:
                 offsets = torch.arange(2, dtype=torch.int64, device=dev) * Ns   # [0, Ns], made on the device
-        elif polish or adaptive:
+        elif polish or adaptive or guided:
             offsets = np.array([0, Ns], dtype=np.int64)
-        if adaptive:                                                         # the S = 1 scenes call, reshaped to the one-scene dict
+        if adaptive or guided:                                               # the S = 1 scenes call, reshaped to the one-scene dict
+            more = dict(confidence=adaptive[0], first_round=adaptive[1]) if adaptive else {}
             r = self.robust_pose_scenes(method, sc, offsets, calm, n_hyp, threshold, seed=seed, n_sample=n_sample, candidates=candidates,
-                                        lo_rounds=lo_rounds, ns_max=Ns, confidence=adaptive[0], first_round=adaptive[1])
+                                        lo_rounds=lo_rounds, ns_max=Ns, order=order, quality=quality, growth=growth, **more)
             one = (lambda a: a[0].item()) if host else (lambda a: a[0])
             out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
                        refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
             if "score" in r:
                 out["score"] = one(r["score"])
-            out["n_hyp_used"] = one(r["n_hyp_used"])
+            if adaptive:
+                out["n_hyp_used"] = one(r["n_hyp_used"])
         else:
             mid = METHOD_IDS[method]
             args = (int(seed), int(n_hyp), 0 if n_sample is None else int(n_sample), float(threshold), int(candidates), int(lo_rounds))
@@ -959,7 +1097,7 @@ class Context:
         return calm_cm.to(device=dev, dtype=torch.float64), stride
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
-                           polish=False, refine=None, confidence=None, first_round=256):
+                           polish=False, refine=None, confidence=None, first_round=256, order=None, quality=None, growth=200000):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
@@ -976,8 +1114,15 @@ class Context:
         confidence = c in (0, 1): the early stop (tff_robust_pose_scenes_adaptive_*).  Hypotheses are drawn in rounds ending at round_plan(c, n_hyp,
         first_round)[0] per scene, n_hyp being the cap, and a scene stops after the round at which adaptive_stop holds for its best hypothesis; n_hyp_used
         (S,) int32 joins the dict (0 for a scene that never ran), and scene s gets bit for bit what robust_pose gives for it alone with n_hyp =
-        n_hyp_used[s] and seed + s.  Still no synchronisation on the device path.  Without a confidence nothing changes and the key is absent."""
+        n_hyp_used[s] and seed + s.  Still no synchronisation on the device path.  Without a confidence nothing changes and the key is absent.
+        order= or quality= (at most one): quality-guided (PROSAC) sampling, tff_robust_pose_scenes_guided_*.  order (Ntot,) int32 holds every scene's
+        ranking, best first, as local indices 0 .. n_s - 1, packed like the scenes (numpy on the host path, a CUDA tensor on the device path); quality
+        (Ntot,) float, higher is better and NaN last, is turned into it by stable sorts (order_from_quality; torch on the device path, no
+        synchronisation).  The early hypotheses draw from the best-ranked matches, and after `growth` draws per scene the sampling is the uniform one
+        (sample_indices_guided_reference is the definition).  Scene s still equals its own one-scene call with seed + s, and confidence, refine, polish
+        and set_score("msac") compose as without a ranking; the stop rule is the existing one.  Without either argument growth is ignored."""
         adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
+        guided = self._check_guided(scenes, order, quality, growth)
         if refine is not None and refine not in RAGGED_METHODS:
             raise ValueError("robust_pose_scenes refines with one of %s, not %r" % (", ".join(RAGGED_METHODS), refine))
         if method not in ROBUST_METHODS:
@@ -999,7 +1144,15 @@ class Context:
             Rt2 = np.empty((S, 12)); Rt3 = np.empty((S, 12)); T = np.empty((S, 27))
             mask = np.zeros(sc.shape[0], dtype=np.uint8); info = np.zeros((S, 4), dtype=np.int32); st = np.zeros(S, dtype=np.int32)
             ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
-            if adaptive is None:
+            if guided is not None:
+                rank = guided[1] if guided[0] == "order" else order_from_quality(guided[1], offsets)
+                rank = np.ascontiguousarray(rank, dtype=np.int32) if rank.shape[0] else np.zeros(1, dtype=np.int32)
+                used = np.zeros(S, dtype=np.int32) if adaptive is not None else None
+                _check(self.lib, self.lib.tff_robust_pose_scenes_guided_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args,
+                                                                             *(adaptive or (0.0, 0)), ptr(rank), guided[2], ptr(Rt2), ptr(Rt3), ptr(T),
+                                                                             ptr(mask), ptr(info), ptr(used) if used is not None else None, ptr(st)),
+                       "tff_robust_pose_scenes_guided_host")
+            elif adaptive is None:
                 _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
                                                                       ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
             else:
@@ -1040,7 +1193,22 @@ class Context:
         mask = torch.empty(ntot, dtype=torch.uint8, device=dev)
         info = torch.empty((S, 4), dtype=torch.int32, device=dev); st = torch.empty(S, dtype=torch.int32, device=dev)
         self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        if adaptive is None:
+        if guided is not None:
+            rank = guided[1]
+            if guided[0] == "quality":                                       # stable sorts on the device: by descending quality, then by scene; nothing is read back
+                q = torch.where(torch.isnan(rank), torch.full_like(rank, float("-inf")), rank).to(torch.float64)
+                by_q = torch.argsort(-q, stable=True)
+                scene = torch.searchsorted(offsets, torch.arange(ntot, dtype=torch.int64, device=dev), right=True) - 1   # -1 in front of offsets[0], S behind offsets[S]
+                glob = by_q[torch.argsort(scene[by_q], stable=True)]
+                sg = scene[glob]
+                rank = torch.where((sg >= 0) & (sg < S), glob - offsets[sg.clamp(0, S)], torch.full_like(glob, -1)).to(torch.int32)
+            rank = rank.contiguous() if ntot else torch.zeros(1, dtype=torch.int32, device=dev)
+            used = torch.zeros(S, dtype=torch.int32, device=dev) if adaptive is not None else None
+            _check(self.lib, self.lib.tff_robust_pose_scenes_guided_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S,
+                                                                        self._p(calm_cm), stride, *args, *(adaptive or (0.0, 0)), self._p(rank), guided[2],
+                                                                        self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info), self._p(used),
+                                                                        self._p(st)), "tff_robust_pose_scenes_guided_dev")
+        elif adaptive is None:
             _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
                                                                  stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
                                                                  self._p(st)), "tff_robust_pose_scenes_dev")

@@ -19,6 +19,7 @@
 #include "ragged_kernel.h"
 #include "robust_kernel.h"
 #include "robust_scenes_kernel.h"
+#include "robust_guided_kernel.h"
 #include "ba_ragged_kernel.h"
 
 namespace {
@@ -76,6 +77,7 @@ struct tff_ctx {
     DevBuf in, calm, out, idx, scratch_status, gh_rec, gh_topt, gh_init, spill, pre_rec, retry;
     DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
     DevBuf robust_hyp, robust_counts, robust_cand;   // the robust estimators, one scene or many: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust_scenes)
+    DevBuf guided_ends, guided_order;      // guided sampling: the pool tables (4 n_total bytes), the ranking of a _host call (4 n_total bytes)
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
@@ -814,6 +816,8 @@ struct ScenesCall {
     double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
     const RoundPlan* plan = nullptr;         // tff_robust_pose_scenes_adaptive_*: the rounds, and ...
     int32_t* used = nullptr;                 // ... S: the hypotheses each scene drew
+    const int32_t* order = nullptr;          // tff_robust_pose_scenes_guided_*: n_total ranks, packed like the scenes (null: the uniform sampler), and ...
+    int64_t growth = 0;                      // ... the number of draws after which the guided sampler is the uniform one
 };
 // The rounds of the adaptive call (include/tftfund.h): round r ends at ends[r - 1] = min(n_hyp, first_round << (r - 1)) hypotheses per scene, and a scene
 // stops there once w^n_sample >= qmin[r - 1] = -expm1(log1p(-confidence) / ends[r - 1]) for the inlier ratio w of its best hypothesis
@@ -895,6 +899,17 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         TFF_TRY(c->retry.reserve(((size_t)chunk + 2) * sizeof(int32_t)));
         if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
     }
+    if (q.order) {                                                           // the pool tables' workspace, before anything of this call is on the stream
+        TFF_TRY(c->guided_ends.reserve((size_t)(q.n_total ? q.n_total : 1) * sizeof(int32_t)));
+        if (!q.plan && q.used) TFF_HIP(hipMemsetD32Async((hipDeviceptr_t)q.used, (int)q.n_hyp, (size_t)S, c->stream));   // a fixed n_hyp: used[s] = n_hyp
+    }
+    int32_t* g_ends = (int32_t*)c->guided_ends.p;
+    // the sampler of the call: k_scenes_sample, or its guided variant over the pool tables (robust_guided_kernel.h)
+    auto sample = [&](const tff::ScenesSampleArgs& a) {
+        const unsigned grid = (unsigned)((a.B + 255) / 256);
+        if (!q.order) return launch(c, tff::k_scenes_sample, grid, 256, 0, a);
+        return launch(c, tff::k_scenes_sample_guided, grid, 256, 0, tff::ScenesSampleGuidedArgs{a, g_ends, q.order});
+    };
     if (q.n_total) TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
     // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate (per-scene CalM only) | flags | the packed refit batch
     size_t off = 0;
@@ -925,6 +940,9 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
         if (q.plan) TFF_HIP(hipMemsetAsync(q.used, 0, (size_t)S * sizeof(int32_t), c->stream));
         return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
     }
+    // 0. guided sampling only: every scene's pool table, one workgroup per scene
+    if (q.order)
+        TFF_TRY(launch(c, tff::k_guided_ends, (unsigned)(S < 65536 ? S : 65536), tff::GUIDED_ENDS_THREADS, 0, tff::GuidedEndsArgs{set, (long)q.growth, n, g_ends}));
 
     // one chunk of hypotheses: poses (51 doubles) | CalM (27, per-scene CalM only) | status | sample indices
     TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
@@ -957,8 +975,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
             const int64_t e_end = q.plan->ends[r], len = e_end - e_prev, Gr = S * len;
             for (int64_t first = 0; first < Gr; first += chunk) {
                 const int64_t B = Gr - first < chunk ? Gr - first : chunk;
-                TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
-                               tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)len, n, h_idx, h_calm, (long)e_prev, live}));
+                TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)len, n, h_idx, h_calm, (long)e_prev, live}));
                 TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
                 TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, len, q.threshold, dense, live));
                 TFF_TRY(launch(c, tff::k_round_scatter, (unsigned)((B + 255) / 256), 256, 0,
@@ -972,8 +989,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     // 1. hypotheses and their counts, chunk by chunk over g = s * n_hyp + h
     for (int64_t first = 0; !q.plan && first < G; first += chunk) {
         const int64_t B = G - first < chunk ? G - first : chunk;
-        TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0,
-                       tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
+        TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
         TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
         // The one branch on the form of the call: without offsets (tff_robust_pose_dev: one valid scene [0, n_total), shared CalM) the hypotheses are counted
         // by the one-scene launcher, whose one-wavefront-per-hypothesis route serves a few thousand hypotheses better than sixteen per workgroup.  Measured
@@ -995,8 +1011,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
             TFF_TRY(launch(c, tff::k_robust_topk, dim3((unsigned)topk_blocks, sy), tff::ROBUST_TOPK_THREADS, 0,
                            tff::RobustTopkArgs{counts + s0 * q.n_hyp, (long)q.n_hyp, sel + s0 * K, r, K}));
     }
-    TFF_TRY(launch(c, tff::k_scenes_sample, (unsigned)((C + 255) / 256), 256, 0,
-                   tff::ScenesSampleArgs{set, (unsigned long long)q.seed, 0, sel, (long)C, (long)K, n, c_idx, c_calm}));
+    TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, 0, sel, (long)C, (long)K, n, c_idx, c_calm}));
     TFF_TRY(sampled(c_idx, c_calm, C, s.pose, s.status));
     TFF_TRY(launch(c, tff::k_robust_seed, (unsigned)((C + 63) / 64), 64, 0, s));
     // 3. local optimisation, the candidates of all scenes at once: flags -> packed inliers -> one ragged refit -> counts -> adopt
@@ -1026,7 +1041,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 104; }
+int tff_version(void) { return 105; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1052,7 +1067,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->ba_plan, &c->ba_pack, &c->ba_host})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host})
         b->release();
     delete c;
 }
@@ -1255,7 +1270,7 @@ int tff_robust_pose_scenes_dev(tff_ctx* c, int32_t method, const double* scenes,
 static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                               int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
                               double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status, const double* confidence,
-                              int32_t first_round, int32_t* used) {
+                              int32_t first_round, int32_t* used, const int32_t* order = nullptr, int64_t growth = 0) {
     if (S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
     if (!scene_offsets) return fail(TFF_E_INVALID, "null offsets");
     if (scene_offsets[0] < 0) return fail(TFF_E_INVALID, "robust estimation: negative offset");
@@ -1285,6 +1300,7 @@ static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, 
     TFF_TRY(c->ragged_off.reserve((nS + 1) * sizeof(int64_t)));
     TFF_TRY(c->out.reserve(nS * 51 * sizeof(double) + (size_t)n_total + 8));
     TFF_TRY(c->idx.reserve(nS * 6 * sizeof(int32_t)));
+    if (order) TFF_TRY(c->guided_order.reserve((size_t)(n_total ? n_total : 1) * sizeof(int32_t)));   // the guided form: the ranking's copy
     ScenesCall d = h;
     d.scenes = (const double*)c->in.p; d.calm = (const double*)c->calm.p; d.offsets = (const int64_t*)c->ragged_off.p;
     d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + nS * 12; d.T = d.Rt3 + nS * 12; d.mask = (uint8_t*)(d.T + nS * 27);
@@ -1292,6 +1308,11 @@ static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, 
     if (nscene) TFF_HIP(hipMemcpyAsync(c->in.p, scenes, nscene, hipMemcpyHostToDevice, c->stream));
     TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
     TFF_HIP(hipMemcpyAsync(c->ragged_off.p, scene_offsets, (nS + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (order) {                                                             // the guided form: the ranking travels like the scenes
+        if (n_total) TFF_HIP(hipMemcpyAsync(c->guided_order.p, order, (size_t)n_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        d.order = (const int32_t*)c->guided_order.p; d.growth = growth;
+        if (!confidence) d.used = nullptr;                                   // (a fixed n_hyp: the caller's used, if any, is filled on the host)
+    }
     TFF_TRY(launch_robust_scenes(c, *route, d));
     TFF_HIP(hipMemcpyAsync(Rt2, d.Rt2, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     TFF_HIP(hipMemcpyAsync(Rt3, d.Rt3, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1357,6 +1378,63 @@ int tff_robust_pose_scenes_adaptive_host(tff_ctx* c, int32_t method, const doubl
     TFF_ENTER(c);
     return robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
                               info, status, &confidence, first_round, used);
+}
+
+// ---- quality-guided sampling (include/tftfund_guided.h; kernels in robust_guided_kernel.h) -----------------------------------------------------------
+// the two arguments every guided entry point adds, refused first
+static int check_guided(const int32_t* order, int64_t growth) {
+    if (!order) return fail(TFF_E_INVALID, "guided sampling: null order");
+    if (growth < 1 || growth > (int64_t)tff::GUIDED_MAX_GROWTH) return fail(TFF_E_INVALID, "guided sampling: growth must be between 1 and 2^31 - 2^25");
+    return 0;
+}
+int tff_robust_pose_scenes_guided_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max,
+                                      int64_t S, const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold,
+                                      int32_t n_cand, int32_t lo_rounds, double confidence, int32_t first_round, const int32_t* order, int64_t growth,
+                                      double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    TFF_TRY(check_guided(order, growth));
+    ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    const RaggedRoute* route;
+    TFF_TRY(check_scenes(c, &q, &route));
+    RoundPlan plan;
+    if (confidence != 0.0) {                                                 // 0: a fixed n_hyp, no rounds; anything else is the adaptive call's confidence
+        TFF_TRY(make_round_plan(confidence, n_hyp, first_round, &plan));
+        if (!used) return fail(TFF_E_INVALID, "null pointer");
+        q.plan = &plan;
+    }
+    q.used = used;                                                           // (without a plan: null, or filled with n_hyp by launch_robust_scenes)
+    q.order = order; q.growth = growth;
+    if (S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    return launch_robust_scenes(c, *route, q);
+}
+int tff_robust_pose_scenes_guided_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
+                                       int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
+                                       int32_t lo_rounds, double confidence, int32_t first_round, const int32_t* order, int64_t growth, double* Rt2,
+                                       double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    TFF_TRY(check_guided(order, growth));
+    TFF_TRY(robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
+                               info, status, confidence != 0.0 ? &confidence : nullptr, first_round, used, order, growth));
+    if (confidence == 0.0 && used)
+        for (int64_t s = 0; s < S; ++s) used[s] = (int32_t)n_hyp;
+    return 0;
+}
+int tff_sample_indices_guided_dev(tff_ctx* c, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, const int32_t* order, int64_t growth,
+                                  int32_t* sample_idx) {
+    TFF_ENTER(c);
+    TFF_TRY(check_guided(order, growth));
+    if (n < 1 || n > tff::ROBUST_MAX_SAMPLE || Ns < n || Ns > RAGGED_MAX_N || B < 0 || first < 0)
+        return fail(TFF_E_INVALID, "sample_indices_guided: need 1 <= n <= 16, n <= Ns <= 2^24, B >= 0, first >= 0");
+    return run_batch(c, B, sample_idx != nullptr, "null pointer", nullptr, [&] {
+        TFF_TRY(c->guided_ends.reserve((size_t)Ns * sizeof(int32_t)));      // (before the table's launch: nothing of this call is on the stream yet)
+        int32_t* ends = (int32_t*)c->guided_ends.p;
+        const tff::SceneSet one{nullptr, nullptr, 1, (long)Ns, Ns, n, nullptr, 0};
+        TFF_TRY(launch(c, tff::k_guided_ends, 1, tff::GUIDED_ENDS_THREADS, 0, tff::GuidedEndsArgs{one, (long)growth, n, ends}));
+        return launch(c, tff::k_sample_indices_guided, (unsigned)((B + 255) / 256), 256, 0,
+                      tff::SampleGuidedArgs{tff::SampleArgs{(unsigned long long)seed, (long)first, (long)B, n, Ns, sample_idx}, ends, order});
+    });
 }
 
 int tff_inlier_count_scenes_dev(tff_ctx* c, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int64_t S, const double* calm,
