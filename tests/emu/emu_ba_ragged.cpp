@@ -1,13 +1,7 @@
 // TEST INFRASTRUCTURE ONLY: the chain of csrc/ba_ragged_kernel.h around k_bundle_adjust, compiled by g++ against the lane emulator (hip_emu.h), for
 // tests/test_emulated_ba_ragged.py.  The caller owns every workspace, so the test can look at the plan.
 #include <vector>
-#include "hip_emu.h"
-inline unsigned long long __ballot(bool p) {
-    uint64_t c = p ? (1ull << (emu::tl_threadIdx.x & 63u)) : 0ull;
-    for (int m = 32; m >= 1; m >>= 1) c |= emu::exchange(c, (int)((emu::tl_threadIdx.x & 63u) ^ (unsigned)m));
-    return c;
-}
-inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+#include "emu_primitives.h"
 #include "launch.h"
 #include "ba_ragged_kernel.h"
 using namespace tff;

@@ -1,23 +1,11 @@
 // TEST INFRASTRUCTURE ONLY: the kernels of the guided (PROSAC) sampler (csrc/robust_guided_kernel.h) compiled by g++ against the lane emulator
-// (hip_emu.h), for tests/test_emulated_guided.py.  The four primitives below are what robust_kernel.h uses beyond wave.h.
+// (hip_emu.h), for tests/test_emulated_guided.py.  emu_primitives.h: what robust_kernel.h uses beyond wave.h.
 #include <vector>
-#include "hip_emu.h"
-inline unsigned long long __shfl_xor(unsigned long long v, int d, int) { return emu::exchange(v, (int)((emu::tl_threadIdx.x & 63u) ^ (unsigned)d)); }
-inline unsigned long long __ballot(bool p) {
-    uint64_t c = p ? (1ull << (emu::tl_threadIdx.x & 63u)) : 0ull;
-    for (int m = 32; m >= 1; m >>= 1) c |= emu::exchange(c, (int)((emu::tl_threadIdx.x & 63u) ^ (unsigned)m));
-    return c;
-}
+#include "emu_primitives.h"
 inline int __shfl_up(int v, unsigned d, int) {                               // (every lane exchanges; the lanes below d keep their own value)
     const unsigned lane = emu::tl_threadIdx.x & 63u;
     const int u = (int)(unsigned)emu::exchange((uint64_t)(unsigned)v, (int)((lane - d) & 63u));
     return lane >= d ? u : v;
-}
-inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
-    unsigned long long o = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (o < v && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return o;
 }
 #include "launch.h"
 #include "robust_guided_kernel.h"
@@ -36,6 +24,12 @@ void g_sample(const long* off, long S, long n_total, int ns_max, int m, const do
               const unsigned long long* keys, long B, long len, int* out, double* calm_out, long base, const int* live, const int* ends, const int* order) {
     ScenesSampleArgs a{mk(off, S, n_total, ns_max, m, calm, cs), seed, first, keys, B, len, m, out, calm_out, base, live};
     emu::launch(k_scenes_sample_guided, (unsigned)((B + 255) / 256), 256, 0, ScenesSampleGuidedArgs{a, ends, order});
+}
+// k_scenes_sample, the uniform sampler, over the same rows
+void g_sample_uniform(const long* off, long S, long n_total, int ns_max, int m, const double* calm, long cs, unsigned long long seed, long first,
+                      const unsigned long long* keys, long B, long len, int* out, double* calm_out, long base, const int* live) {
+    ScenesSampleArgs a{mk(off, S, n_total, ns_max, m, calm, cs), seed, first, keys, B, len, m, out, calm_out, base, live};
+    emu::launch(k_scenes_sample, (unsigned)((B + 255) / 256), 256, 0, a);
 }
 // k_sample_indices_guided for one scene whose table is `ends`
 void g_sample_one(unsigned long long seed, long first, long B, int m, int Ns, int* out, const int* ends, const int* order) {

@@ -1,19 +1,7 @@
 // TEST INFRASTRUCTURE ONLY: the count kernels of csrc/blocks_kernel.h and csrc/robust_scenes_kernel.h in their count and MSAC forms (TFF_OPT_SCORE), and
 // k_triangulate as the source of the reference's points, compiled by g++ against the lane emulator (hip_emu.h), for tests/test_emulated_score.py.
 #include <vector>
-#include "hip_emu.h"
-inline unsigned long long __shfl_xor(unsigned long long v, int d, int) { return emu::exchange(v, (int)((emu::tl_threadIdx.x & 63u) ^ (unsigned)d)); }
-inline unsigned long long __ballot(bool p) {
-    uint64_t c = p ? (1ull << (emu::tl_threadIdx.x & 63u)) : 0ull;
-    for (int m = 32; m >= 1; m >>= 1) c |= emu::exchange(c, (int)((emu::tl_threadIdx.x & 63u) ^ (unsigned)m));
-    return c;
-}
-inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
-    unsigned long long o = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (o < v && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return o;
-}
+#include "emu_primitives.h"
 #include "launch.h"
 #include "robust_scenes_kernel.h"
 using namespace tff;

@@ -24,7 +24,7 @@ def _lib():
     out_dir = os.path.join(emu, "_build")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "libtff_emu_guided.so")
-    deps = [os.path.join(emu, f) for f in ("emu_guided.cpp", "hip_emu.h", "wave_target.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
+    deps = [os.path.join(emu, f) for f in ("emu_guided.cpp", "emu_primitives.h", "hip_emu.h", "wave_target.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
     if not os.path.exists(out) or any(os.path.getmtime(p) > os.path.getmtime(out) for p in deps):
         subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-pthread", "-shared", "-fPIC", "-I" + emu, "-I" + csrc, "-o", out,
                         os.path.join(emu, "emu_guided.cpp")], check=True)
@@ -129,3 +129,34 @@ def test_one_scene_kernel_is_the_twin():
         out = np.zeros((300, m), dtype=np.int32)
         L.g_sample_one(c_u(77), c_l(first), c_l(300), c_i(m), c_i(Ns), P(out), P(ends), P(order))
         assert np.array_equal(out, api.sample_indices_guided_reference(77, first, 300, m, order, growth)), (Ns, m, growth)
+
+
+def test_guided_kernel_is_the_uniform_one_beyond_the_table_and_for_dead_and_invalid_scenes():
+    """k_scenes_sample_guided and k_scenes_sample share their row function: with the identity ranking the two kernels agree index for index wherever the
+    guided draw is the uniform one (hypothesis h + 1 beyond ends[N]), and for every row of a dead or an invalid scene (-1 from both); the CalM copies agree
+    everywhere.  Two scenes of 9 and 7 correspondences, n = 7, growth = 1, 12 hypotheses per scene."""
+    L = _lib()
+    sizes, m, growth, n_hyp, seed = [9, 7], 7, 1, 12, 2024
+    off = np.array([0, 9, 16], dtype=np.int64)
+    ident = np.concatenate([np.arange(n) for n in sizes]).astype(np.int32)
+    calms = np.arange(2 * 27, dtype=np.float64).reshape(2, 27)
+    ends = np.full(16, -7, dtype=np.int32)
+    L.g_ends(P(off), c_l(2), c_l(16), c_i(9), c_i(m), c_l(growth), P(ends), c_i(2))
+    last = [int(api.guided_pool_ends(n, m, growth)[-1]) for n in sizes]      # ends[N] per scene
+    assert [int(ends[8]), int(ends[15])] == last and all(0 < e < n_hyp for e in last)
+    B = 2 * n_hyp
+    for ns_max, live, quiet in ((9, None, ()), (9, np.array([0, 1], dtype=np.int32), (0,)), (9, np.array([1, 0], dtype=np.int32), (1,)), (8, None, (0,))):
+        got = np.full((B, m), -7, dtype=np.int32); want = np.full((B, m), -7, dtype=np.int32)
+        cg = np.zeros((B, 27)); cu = np.zeros((B, 27))
+        L.g_sample(P(off), c_l(2), c_l(16), c_i(ns_max), c_i(m), P(calms), c_l(27), c_u(seed), c_l(0), None, c_l(B), c_l(n_hyp), P(got), P(cg), c_l(0),
+                   P(live), P(ends), P(ident))
+        L.g_sample_uniform(P(off), c_l(2), c_l(16), c_i(ns_max), c_i(m), P(calms), c_l(27), c_u(seed), c_l(0), None, c_l(B), c_l(n_hyp), P(want), P(cu),
+                           c_l(0), P(live))
+        assert np.array_equal(cg, cu) and np.array_equal(cu, np.repeat(calms, n_hyp, axis=0))
+        for s in range(2):
+            rows = slice(s * n_hyp, (s + 1) * n_hyp)
+            if s in quiet:                                                    # dead (live[s] == 0) or invalid (9 > ns_max = 8): a row of -1 from both
+                assert (got[rows] == -1).all() and (want[rows] == -1).all(), (ns_max, s)
+            else:                                                             # beyond the table: the uniform draw, through the identity ranking
+                assert np.array_equal(got[rows][last[s]:], want[rows][last[s]:]), (ns_max, s)
+                assert (want[rows] >= off[s]).all() and (want[rows] < off[s + 1]).all()

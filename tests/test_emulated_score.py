@@ -36,7 +36,7 @@ def _lib():
     out_dir = os.path.join(emu, "_build")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "libtff_emu_score.so")
-    deps = [os.path.join(emu, f) for f in ("emu_score.cpp", "hip_emu.h", "wave_target.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
+    deps = [os.path.join(emu, f) for f in ("emu_score.cpp", "emu_primitives.h", "hip_emu.h", "wave_target.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
     if not os.path.exists(out) or any(os.path.getmtime(p) > os.path.getmtime(out) for p in deps):
         subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-pthread", "-shared", "-fPIC", "-I" + emu, "-I" + csrc, "-o", out,
                         os.path.join(emu, "emu_score.cpp")], check=True)

@@ -209,6 +209,16 @@ GUIDED_MAX_GROWTH = 2 ** 31 - 2 ** 25   # the largest `growth` of the guided sam
 GUIDED_MAX_N = 1 << 24       # ... for scenes of up to 2^24 correspondences, the bound of every robust call
 
 
+# the entry point of Context.robust_pose_scenes (without its _host / _dev), by (ranking given, confidence given)
+_ROBUST_SCENES_ENTRY = {(False, False): "tff_robust_pose_scenes", (False, True): "tff_robust_pose_scenes_adaptive",
+                        (True, False): "tff_robust_pose_scenes_guided", (True, True): "tff_robust_pose_scenes_guided"}
+
+
+def _np_ptr(a):
+    """the pointer function of the _host forms (Context._p is that of the _dev forms); None is the null pointer"""
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
 def _check_adaptive(confidence, first_round):
     """the adaptive arguments of robust_pose / robust_pose_scenes, refused as the library refuses them"""
     c = float(confidence)
@@ -1032,45 +1042,34 @@ class Context:
                 offsets = torch.arange(2, dtype=torch.int64, device=dev) * Ns   # [0, Ns], made on the device
         elif polish or adaptive or guided:
             offsets = np.array([0, Ns], dtype=np.int64)
-        if adaptive or guided:                                               # the S = 1 scenes call, reshaped to the one-scene dict
+        if adaptive or guided:                                               # the S = 1 scenes call ...
             more = dict(confidence=adaptive[0], first_round=adaptive[1]) if adaptive else {}
             r = self.robust_pose_scenes(method, sc, offsets, calm, n_hyp, threshold, seed=seed, n_sample=n_sample, candidates=candidates,
                                         lo_rounds=lo_rounds, ns_max=Ns, order=order, quality=quality, growth=growth, **more)
-            one = (lambda a: a[0].item()) if host else (lambda a: a[0])
-            out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
-                       refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
-            if "score" in r:
-                out["score"] = one(r["score"])
-            if adaptive:
-                out["n_hyp_used"] = one(r["n_hyp_used"])
-        else:
-            mid = METHOD_IDS[method]
+        else:                                                                # ... or the one-scene entry point, its outputs those of S = 1
             args = (int(seed), int(n_hyp), 0 if n_sample is None else int(n_sample), float(threshold), int(candidates), int(lo_rounds))
             if host:
-                calm_cm, _ = self._calm_cm_np(calm, 1)
-                Rt2 = np.empty(12); Rt3 = np.empty(12); T = np.empty(27)
-                mask = np.zeros(Ns, dtype=np.uint8); info = np.zeros(4, dtype=np.int32); st = np.zeros(1, dtype=np.int32)
-                ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
-                _check(self.lib, self.lib.tff_robust_pose_host(self.handle, mid, ptr(sc), Ns, ptr(calm_cm), *args, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask),
-                                                               ptr(info), ptr(st)), "tff_robust_pose_host")
-                out = dict(R_t_2=Rt2.reshape(4, 3).T, R_t_3=Rt3.reshape(4, 3).T, T=T.reshape(3, 3, 3).transpose(2, 1, 0), mask=mask,
-                           inliers=int(info[0]), hypothesis=int(info[1]), refits=int(info[2]), candidates=int(info[3]), status=int(st[0]))
-                if getattr(self, "_score", 0):
-                    out["score"] = int(self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]) if out["status"] == 0 else -1
+                calm_cm, p, name = self._calm_cm_np(calm, 1)[0], _np_ptr, "tff_robust_pose_host"
             else:
-                calm_cm = calm.t().contiguous().reshape(27)
-                Rt2 = torch.empty(12, dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
-                T = torch.empty(27, dtype=torch.float64, device=dev)
-                mask = torch.empty(Ns, dtype=torch.uint8, device=dev)
-                info = torch.empty(4, dtype=torch.int32, device=dev); st = torch.empty(1, dtype=torch.int32, device=dev)
+                calm_cm, p, name = calm.t().contiguous().reshape(27), self._p, "tff_robust_pose_dev"
                 self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-                _check(self.lib, self.lib.tff_robust_pose_dev(self.handle, mid, self._p(sc), Ns, self._p(calm_cm), *args, self._p(Rt2), self._p(Rt3),
-                                                              self._p(T), self._p(mask), self._p(info), self._p(st)), "tff_robust_pose_dev")
-                out = dict(R_t_2=Rt2.reshape(4, 3).t(), R_t_3=Rt3.reshape(4, 3).t(), T=T.reshape(3, 3, 3).permute(2, 1, 0), mask=mask,
-                           inliers=info[0], hypothesis=info[1], refits=info[2], candidates=info[3], status=st[0])
-                if getattr(self, "_score", 0):                               # one more count call on the returned pose; no pose (NaN): -1
-                    sco = self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]
-                    out["score"] = torch.where(st[0] == 0, sco, torch.full_like(sco, -1))
+            o, r = self._robust_outputs(1, Ns, False, None if host else dev)
+            _check(self.lib, getattr(self.lib, name)(self.handle, METHOD_IDS[method], p(sc), Ns, p(calm_cm), *args, *map(p, o[:5]), p(o[6])), name)
+        # ... reshaped to the one-scene dict
+        one = (lambda a: a[0].item()) if host else (lambda a: a[0])
+        out = dict(R_t_2=r["R_t_2"][0], R_t_3=r["R_t_3"][0], T=r["T"][0], mask=r["mask"], inliers=one(r["inliers"]), hypothesis=one(r["hypothesis"]),
+                   refits=one(r["refits"]), candidates=one(r["candidates"]), status=one(r["status"]))
+        if "score" in r:
+            out["score"] = one(r["score"])
+        elif getattr(self, "_score", 0):                                     # the direct call: one more count call on the returned pose; no pose (NaN): -1
+            count = lambda: self.inlier_count(sc, calm, out["R_t_2"][None], out["R_t_3"][None], threshold)[0]
+            if host:
+                out["score"] = int(count()) if out["status"] == 0 else -1
+            else:
+                sco = count()
+                out["score"] = torch.where(out["status"] == 0, sco, torch.full_like(sco, -1))
+        if adaptive:
+            out["n_hyp_used"] = one(r["n_hyp_used"])
         # refine and polish, the same for both forms
         if refine is not None:                                               # (boolean indexing reads the count on the host)
             inl = sc[out["mask"] != 0] if host else sc[out["mask"] != 0].contiguous()
@@ -1084,6 +1083,22 @@ class Context:
                 out["repr_err_polished"] = float(out["repr_err_polished"])
         return out
 
+    @staticmethod
+    def _robust_outputs(S, n_mask, with_used, dev):
+        """the outputs of a robust call of S scenes -- numpy for the _host forms (dev None), else uninitialised tensors on dev, used alone zeroed (the
+        library may leave it unwritten) -> (as the library takes them: Rt2 (S,12), Rt3, T (S,27), mask (n_mask,), info (S,4), used (S,) or None, status
+        (S,); the dict of robust_pose_scenes over them: views that turn the column-major Rt and T into (S,3,4) and (S,3,3,3), numpy or torch alike)"""
+        if dev is None:
+            new = lambda dt, *shape: np.zeros(shape, dtype=dt)
+        else:
+            new = lambda dt, *shape: torch.empty(shape, dtype=getattr(torch, dt), device=dev)
+        Rt2, Rt3, T, mask, info, st = new("float64", S, 12), new("float64", S, 12), new("float64", S, 27), new("uint8", n_mask), new("int32", S, 4), new("int32", S)
+        out = dict(R_t_2=Rt2.reshape(S, 4, 3).swapaxes(1, 2), R_t_3=Rt3.reshape(S, 4, 3).swapaxes(1, 2), T=T.reshape(S, 3, 3, 3).swapaxes(1, 3), mask=mask,
+                   inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
+        if with_used:
+            out["n_hyp_used"] = new("int32", S) if dev is None else torch.zeros(S, dtype=torch.int32, device=dev)
+        return (Rt2, Rt3, T, mask, info, out.get("n_hyp_used"), st), out
+
     def _calm_scenes(self, calm, S, dev):
         """(9, 3) or (S, 9, 3) numpy / torch CalM -> (column-major flat tensor on dev, calm_stride)"""
         if isinstance(calm, np.ndarray):
@@ -1095,6 +1110,23 @@ class Context:
         else:
             calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(S * 27), 27
         return calm_cm.to(device=dev, dtype=torch.float64), stride
+
+    def _robust_scenes_call(self, dev, mid, scenes, offsets, sizes, S, calm_cm, stride, scalars, adaptive, ranking):
+        """the library call of robust_pose_scenes, _host (dev None) or _dev (sizes: the two it adds), assembled once: handle and inputs, the six scalars,
+        confidence and first_round if any, ranking and growth if any, the outputs, used if the form has it, status -> the result dict"""
+        p = _np_ptr if dev is None else self._p
+        name = _ROBUST_SCENES_ENTRY[ranking is not None, adaptive is not None] + ("_host" if dev is None else "_dev")
+        o, out = self._robust_outputs(S, scenes.shape[0], adaptive is not None, dev)
+        a = (self.handle, mid, p(scenes), p(offsets)) + sizes + (S, p(calm_cm), stride) + scalars
+        if ranking is not None:                                              # (rank, growth); without a confidence: 0.0, a fixed n_hyp
+            a += (adaptive or (0.0, 0)) + (p(ranking[0]), ranking[1])
+        elif adaptive is not None:
+            a += adaptive
+        a += tuple(map(p, o[:5]))
+        if ranking is not None or adaptive is not None:
+            a += (p(o[5]),)
+        _check(self.lib, getattr(self.lib, name)(*a, p(o[6])), name)
+        return out
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
                            polish=False, refine=None, confidence=None, first_round=256, order=None, quality=None, growth=200000):
@@ -1140,37 +1172,17 @@ class Context:
             if offsets[-1] > sc.shape[0]:
                 raise ValueError("offsets[-1] = %d beyond the %d packed correspondences" % (offsets[-1], sc.shape[0]))
             calm_cm, stride = self._calm_cm_np(calm, S)
-            ntot = int(offsets[-1])
-            Rt2 = np.empty((S, 12)); Rt3 = np.empty((S, 12)); T = np.empty((S, 27))
-            mask = np.zeros(sc.shape[0], dtype=np.uint8); info = np.zeros((S, 4), dtype=np.int32); st = np.zeros(S, dtype=np.int32)
-            ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+            ranking = None
             if guided is not None:
                 rank = guided[1] if guided[0] == "order" else order_from_quality(guided[1], offsets)
-                rank = np.ascontiguousarray(rank, dtype=np.int32) if rank.shape[0] else np.zeros(1, dtype=np.int32)
-                used = np.zeros(S, dtype=np.int32) if adaptive is not None else None
-                _check(self.lib, self.lib.tff_robust_pose_scenes_guided_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args,
-                                                                             *(adaptive or (0.0, 0)), ptr(rank), guided[2], ptr(Rt2), ptr(Rt3), ptr(T),
-                                                                             ptr(mask), ptr(info), ptr(used) if used is not None else None, ptr(st)),
-                       "tff_robust_pose_scenes_guided_host")
-            elif adaptive is None:
-                _check(self.lib, self.lib.tff_robust_pose_scenes_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args, ptr(Rt2),
-                                                                      ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(st)), "tff_robust_pose_scenes_host")
-            else:
-                used = np.zeros(S, dtype=np.int32)
-                _check(self.lib, self.lib.tff_robust_pose_scenes_adaptive_host(self.handle, mid, ptr(sc), ptr(offsets), S, ptr(calm_cm), stride, *args,
-                                                                               *adaptive, ptr(Rt2), ptr(Rt3), ptr(T), ptr(mask), ptr(info), ptr(used),
-                                                                               ptr(st)), "tff_robust_pose_scenes_adaptive_host")
-            assert ntot <= mask.shape[0]
-            out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(0, 2, 1), R_t_3=Rt3.reshape(S, 4, 3).transpose(0, 2, 1),
-                       T=T.reshape(S, 3, 3, 3).transpose(0, 3, 2, 1), mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2],
-                       candidates=info[:, 3], status=st)
-            if adaptive is not None:
-                out["n_hyp_used"] = used
+                ranking = (np.ascontiguousarray(rank, dtype=np.int32) if rank.shape[0] else np.zeros(1, dtype=np.int32), guided[2])
+            assert int(offsets[-1]) <= sc.shape[0]
+            out = self._robust_scenes_call(None, mid, sc, offsets, (), S, calm_cm, stride, args, adaptive, ranking)
             if getattr(self, "_score", 0):
                 sco = self.inlier_count_scenes(sc, offsets, calm, out["R_t_2"], out["R_t_3"], threshold).cpu().numpy() if S else np.zeros(0, dtype=np.int32)
-                out["score"] = np.where(st == 0, sco, -1).astype(np.int32)
+                out["score"] = np.where(out["status"] == 0, sco, -1).astype(np.int32)
             if refine is not None:
-                keep = mask != 0
+                keep = out["mask"] != 0
                 inl = np.ascontiguousarray(sc[keep])
                 cum = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
                 self._refined(out, self.pose_batch_ragged(refine, inl, cum[offsets], calm, reconst=False))
@@ -1188,11 +1200,8 @@ class Context:
         calm_cm, stride = self._calm_scenes(calm, S, dev)
         if ns_max is None:                                                   # one synchronisation; pass ns_max to avoid it
             ns_max = max(0, int((offsets[1:] - offsets[:-1]).max().item())) if S > 0 else 0
-        Rt2 = torch.empty((S, 12), dtype=torch.float64, device=dev); Rt3 = torch.empty_like(Rt2)
-        T = torch.empty((S, 27), dtype=torch.float64, device=dev)
-        mask = torch.empty(ntot, dtype=torch.uint8, device=dev)
-        info = torch.empty((S, 4), dtype=torch.int32, device=dev); st = torch.empty(S, dtype=torch.int32, device=dev)
         self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ranking = None
         if guided is not None:
             rank = guided[1]
             if guided[0] == "quality":                                       # stable sorts on the device: by descending quality, then by scene; nothing is read back
@@ -1202,33 +1211,16 @@ class Context:
                 glob = by_q[torch.argsort(scene[by_q], stable=True)]
                 sg = scene[glob]
                 rank = torch.where((sg >= 0) & (sg < S), glob - offsets[sg.clamp(0, S)], torch.full_like(glob, -1)).to(torch.int32)
-            rank = rank.contiguous() if ntot else torch.zeros(1, dtype=torch.int32, device=dev)
-            used = torch.zeros(S, dtype=torch.int32, device=dev) if adaptive is not None else None
-            _check(self.lib, self.lib.tff_robust_pose_scenes_guided_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S,
-                                                                        self._p(calm_cm), stride, *args, *(adaptive or (0.0, 0)), self._p(rank), guided[2],
-                                                                        self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info), self._p(used),
-                                                                        self._p(st)), "tff_robust_pose_scenes_guided_dev")
-        elif adaptive is None:
-            _check(self.lib, self.lib.tff_robust_pose_scenes_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S, self._p(calm_cm),
-                                                                 stride, *args, self._p(Rt2), self._p(Rt3), self._p(T), self._p(mask), self._p(info),
-                                                                 self._p(st)), "tff_robust_pose_scenes_dev")
-        else:
-            used = torch.zeros(S, dtype=torch.int32, device=dev)
-            _check(self.lib, self.lib.tff_robust_pose_scenes_adaptive_dev(self.handle, mid, self._p(scenes), self._p(offsets), ntot, int(ns_max), S,
-                                                                          self._p(calm_cm), stride, *args, *adaptive, self._p(Rt2), self._p(Rt3), self._p(T),
-                                                                          self._p(mask), self._p(info), self._p(used), self._p(st)),
-                   "tff_robust_pose_scenes_adaptive_dev")
-        out = dict(R_t_2=Rt2.reshape(S, 4, 3).transpose(1, 2), R_t_3=Rt3.reshape(S, 4, 3).transpose(1, 2), T=T.reshape(S, 3, 3, 3).permute(0, 3, 2, 1),
-                   mask=mask, inliers=info[:, 0], hypothesis=info[:, 1], refits=info[:, 2], candidates=info[:, 3], status=st)
-        if adaptive is not None:
-            out["n_hyp_used"] = used
+            ranking = (rank.contiguous() if ntot else torch.zeros(1, dtype=torch.int32, device=dev), guided[2])
+        out = self._robust_scenes_call(dev, mid, scenes, offsets, (ntot, int(ns_max)), S, calm_cm, stride, args, adaptive, ranking)
+        st = out["status"]
         if getattr(self, "_score", 0):                                       # one more count call on the returned poses; no pose (NaN): -1
             sco = self.inlier_count_scenes(scenes, offsets, calm, out["R_t_2"], out["R_t_3"], threshold) if S else torch.zeros_like(st)
             out["score"] = torch.where(st == 0, sco, torch.full_like(sco, -1))
         if refine is not None:
             # every scene's inliers first, in scene order, without reading a count: a stable sort of 1 - mask; all Ntot rows are kept, the offsets say
             # where the inliers end (boolean indexing and nonzero would synchronise)
-            keep = (mask != 0).to(torch.int64)
+            keep = (out["mask"] != 0).to(torch.int64)
             packed = scenes[torch.argsort(1 - keep, stable=True)]
             cum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(keep, 0)])
             self._refined(out, self.pose_batch_ragged(refine, packed, cum[offsets.clamp(0, ntot)], calm, reconst=False, n_max=int(ns_max)))

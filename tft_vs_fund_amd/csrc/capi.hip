@@ -20,6 +20,7 @@
 #include "robust_kernel.h"
 #include "robust_scenes_kernel.h"
 #include "robust_guided_kernel.h"
+#include "robust_layout.h"
 #include "ba_ragged_kernel.h"
 
 namespace {
@@ -293,10 +294,14 @@ int launch_pose(tff_ctx* c, const PoseCall& p, pose_kernel kmain, pose_kernel kj
 // The triplets a row kernel flags go to the exact kernel as a compact list: [count 0 | count 1 | B indices].  The row kernel appends to the
 // list itself (one atomic per flagged triplet) and zeroes the OTHER counter for the context's next call; this call's counter was zeroed
 // during the previous call (both at allocation).  No scan of the status array, no launch in between.
-int retry_list_begin(tff_ctx* c, tff::LinearTftArgs* a) {
+int retry_list_reserve(tff_ctx* c, int64_t rows) {                           // (a call of many launches sizes the list once: launch_robust_scenes)
     void* before = c->retry.p;
-    TFF_TRY(c->retry.reserve(((size_t)a->B + 2) * sizeof(int32_t)));
+    TFF_TRY(c->retry.reserve(((size_t)rows + 2) * sizeof(int32_t)));
     if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
+    return 0;
+}
+int retry_list_begin(tff_ctx* c, tff::LinearTftArgs* a) {
+    TFF_TRY(retry_list_reserve(c, a->B));
     a->retry_count = (int*)c->retry.p + c->retry_parity;
     a->retry_zero = (int*)c->retry.p + (1 - c->retry_parity);
     a->retry_list = (a->B < (1L << tff::RETRY_HINT_SHIFT)) ? (int*)c->retry.p + 2 : nullptr;   // (an entry is index | hints << 28; beyond, the exact kernel scans the status array)
@@ -783,46 +788,27 @@ int launch_inlier_count(tff_ctx* c, const double* scene, int32_t Ns, const doubl
 }
 
 // ---- robust estimation (tff_robust_pose_*, tff_robust_pose_scenes_*; kernels and the chunking in robust_kernel.h, robust_scenes_kernel.h) ------------------
-// the arguments check_robust judges: those of the one-scene entry points (the six outputs for its null-pointer test only; the seed is carried along unread)
-struct RobustCall {
-    int32_t method; const double* scene; int32_t Ns; const double* calm; uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold;
-    int32_t n_cand; int32_t lo_rounds;
-    double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
-};
-int32_t robust_min_sample(int32_t method) { return method == TFF_METHOD_LINEAR_F ? 8 : 7; }
-// argument checks shared by every form; n_sample = 0 becomes the method's minimum; *route: the method's ragged chain (the refit)
-int check_robust(const tff_ctx* c, RobustCall* q, const RaggedRoute** route) {
-    if (q->method != TFF_METHOD_LINEAR_TFT && q->method != TFF_METHOD_LINEAR_F)
-        return fail(TFF_E_INVALID, "robust estimation: the method must be TFF_METHOD_LINEAR_TFT or TFF_METHOD_LINEAR_F");
-    const int32_t least = robust_min_sample(q->method);
-    if (q->n_sample == 0) q->n_sample = least;
-    if (q->n_sample < least || q->n_sample > tff::ROBUST_MAX_SAMPLE) return fail(TFF_E_INVALID, "robust estimation: n_sample must be 0 or between the method's minimum (7 / 8) and 16");
-    if (q->Ns < q->n_sample) return fail(TFF_E_INVALID, "robust estimation: fewer correspondences than one sample");
-    if (q->n_hyp < 1 || q->n_hyp > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_hyp must be between 1 and 2^31 - 1");
-    if (q->n_cand < 1 || q->n_cand > tff::ROBUST_MAX_CAND) return fail(TFF_E_INVALID, "robust estimation: n_cand must be between 1 and 64");
-    if (q->lo_rounds < 0 || q->lo_rounds > 8) return fail(TFF_E_INVALID, "robust estimation: lo_rounds must be between 0 and 8");
-    if (!(q->threshold > 0.0) || !(q->threshold <= 1.79769313486231570e308)) return fail(TFF_E_INVALID, "robust estimation: the threshold must be a positive finite number");
-    if (!q->scene || !q->calm || !q->Rt2 || !q->Rt3 || !q->T || !q->mask || !q->info || !q->status) return fail(TFF_E_INVALID, "null pointer");
-    if (q->Ns > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: more than 2^24 correspondences");
-    return ragged_route(c, q->method, route);                                // the refit's refusals: TFF_OPT_ROWS = 0, TFF_OPT_KERNEL = 1
-}
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Every entry point fills one ScenesCall and hands it to robust_dev or robust_host (below, with the entry points); both go through check_scenes and end
+// in launch_robust_scenes, whose workspaces reserve_robust lays out (robust_layout.h).
 
-// one call of the chain: S scenes (S = 1, offsets null, calm_stride 0, n_total = ns_max = Ns: tff_robust_pose_dev)
-struct RoundPlan;
-struct ScenesCall {
-    int32_t method; const double* scenes; const int64_t* offsets; int64_t n_total; int32_t ns_max; int64_t S; const double* calm; int64_t calm_stride;
-    uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold; int32_t n_cand; int32_t lo_rounds;
-    double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
-    const RoundPlan* plan = nullptr;         // tff_robust_pose_scenes_adaptive_*: the rounds, and ...
-    int32_t* used = nullptr;                 // ... S: the hypotheses each scene drew
-    const int32_t* order = nullptr;          // tff_robust_pose_scenes_guided_*: n_total ranks, packed like the scenes (null: the uniform sampler), and ...
-    int64_t growth = 0;                      // ... the number of draws after which the guided sampler is the uniform one
-};
 // The rounds of the adaptive call (include/tftfund.h): round r ends at ends[r - 1] = min(n_hyp, first_round << (r - 1)) hypotheses per scene, and a scene
 // stops there once w^n_sample >= qmin[r - 1] = -expm1(log1p(-confidence) / ends[r - 1]) for the inlier ratio w of its best hypothesis
 constexpr int MAX_ROUNDS = 32;
 struct RoundPlan { int rounds; int64_t ends[MAX_ROUNDS]; double qmin[MAX_ROUNDS]; };
+// one call of the chain, in any form: S scenes, host or device pointers as the function says
+struct ScenesCall {
+    int32_t method; const double* scenes; const int64_t* offsets; int64_t n_total; int32_t ns_max; int64_t S; const double* calm; int64_t calm_stride;
+    uint64_t seed; int64_t n_hyp; int32_t n_sample; double threshold; int32_t n_cand; int32_t lo_rounds;
+    double* Rt2; double* Rt3; double* T; uint8_t* mask; int32_t* info; int32_t* status;
+    bool one_scene = false;                  // tff_robust_pose_*: S = 1, a shared CalM and n_total = ns_max = Ns, judged as the scene's size (check_scenes)
+    bool rounds = false;                     // the early stop: confidence and first_round make ...
+    double confidence = 0.0; int32_t first_round = 0;
+    const RoundPlan* plan = nullptr;         // ... the rounds (check_scenes), and ...
+    int32_t* used = nullptr;                 // ... S: the hypotheses each scene drew
+    bool guided = false;                     // tff_robust_pose_scenes_guided_*: the two arguments below are judged (first) ...
+    const int32_t* order = nullptr;          // ... n_total ranks, packed like the scenes (null: the uniform sampler), and ...
+    int64_t growth = 0;                      // ... the number of draws after which the guided sampler is the uniform one
+};
 int make_round_plan(double confidence, int64_t n_hyp, int32_t first_round, RoundPlan* p) {
     if (!(confidence > 0.0 && confidence < 1.0)) return fail(TFF_E_INVALID, "robust estimation: the confidence must lie strictly between 0 and 1");
     if (first_round < 4 || first_round % 4 != 0) return fail(TFF_E_INVALID, "robust estimation: first_round must be a multiple of 4 and at least 4");
@@ -837,21 +823,58 @@ int make_round_plan(double confidence, int64_t n_hyp, int32_t first_round, Round
     }
     return fail(TFF_E_INVALID, "robust estimation: more than 32 rounds between first_round and n_hyp");
 }
-// what can be refused without the offsets: check_robust's list (the scene size apart: too few correspondences is a per-scene status here) and the sizes
-int check_scenes(const tff_ctx* c, ScenesCall* q, const RaggedRoute** route) {
-    RobustCall r{q->method, q->scenes, INT32_MAX, q->calm, q->seed, q->n_hyp, q->n_sample, q->threshold, q->n_cand, q->lo_rounds,
-                 q->Rt2, q->Rt3, q->T, q->mask, q->info, q->status};
-    if (q->S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
-    if (q->n_total < 0 || q->n_total > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_total must be between 0 and 2^31 - 1");
-    if (q->ns_max < 0 || q->ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: ns_max must be between 0 and 2^24");
-    if (q->calm_stride != 0 && q->calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
-    if (!q->offsets) return fail(TFF_E_INVALID, "null offsets");
-    if (q->n_total == 0) { r.scene = q->calm; r.mask = (uint8_t*)q->calm; }  // (nothing packed, no flags: those two pointers may be null)
-    r.Ns = q->n_sample > 0 ? q->n_sample : tff::ROBUST_MAX_SAMPLE;           // (passes check_robust's scene-size tests)
-    TFF_TRY(check_robust(c, &r, route));
-    q->n_sample = r.n_sample;
+// the two arguments every guided entry point adds, refused first
+int check_guided(const int32_t* order, int64_t growth) {
+    if (!order) return fail(TFF_E_INVALID, "guided sampling: null order");
+    if (growth < 1 || growth > (int64_t)tff::GUIDED_MAX_GROWTH) return fail(TFF_E_INVALID, "guided sampling: growth must be between 1 and 2^31 - 2^25");
+    return 0;
+}
+// The argument checks of every form, in the order the forms have always refused in; n_sample = 0 becomes the method's minimum; *route: the method's ragged
+// chain (the refit); with a confidence *plan becomes the call's rounds.  A list's scene with too few correspondences is a per-scene status, not a refusal.
+// ONE-SCENE VARIANT (q->one_scene): no list to judge, and the two scene-size tests see the real Ns = n_total (TFF_E_INVALID, not a status).
+int check_scenes(const tff_ctx* c, ScenesCall* q, bool host, RoundPlan* plan, const RaggedRoute** route) {
+    if (q->guided) TFF_TRY(check_guided(q->order, q->growth));
+    // a _host list: the offsets are readable, so they are judged here (a _dev list's are a per-scene status), and n_total and ns_max come from them
+    if (host && !q->one_scene) {
+        if (q->S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
+        if (!q->offsets) return fail(TFF_E_INVALID, "null offsets");
+        if (q->offsets[0] < 0) return fail(TFF_E_INVALID, "robust estimation: negative offset");
+        int64_t ns_max = 0;
+        for (int64_t s = 0; s < q->S; ++s) {
+            const int64_t ns = q->offsets[s + 1] - q->offsets[s];
+            if (ns < 0) return fail(TFF_E_INVALID, "robust estimation: decreasing offsets");
+            if (ns > ns_max) ns_max = ns;
+        }
+        if (ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: a scene of more than 2^24 correspondences");
+        q->n_total = q->offsets[q->S]; q->ns_max = (int32_t)ns_max;
+    }
+    if (!q->one_scene) {
+        if (q->S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
+        if (q->n_total < 0 || q->n_total > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_total must be between 0 and 2^31 - 1");
+        if (q->ns_max < 0 || q->ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: ns_max must be between 0 and 2^24");
+        if (q->calm_stride != 0 && q->calm_stride != 27) return fail(TFF_E_INVALID, "calm_stride must be 0 (shared CalM) or 27");
+        if (!q->offsets) return fail(TFF_E_INVALID, "null offsets");
+    }
+    if (q->method != TFF_METHOD_LINEAR_TFT && q->method != TFF_METHOD_LINEAR_F)
+        return fail(TFF_E_INVALID, "robust estimation: the method must be TFF_METHOD_LINEAR_TFT or TFF_METHOD_LINEAR_F");
+    const int32_t least = q->method == TFF_METHOD_LINEAR_F ? 8 : 7;
+    if (q->n_sample == 0) q->n_sample = least;
+    if (q->n_sample < least || q->n_sample > tff::ROBUST_MAX_SAMPLE) return fail(TFF_E_INVALID, "robust estimation: n_sample must be 0 or between the method's minimum (7 / 8) and 16");
+    if (q->one_scene && q->n_total < q->n_sample) return fail(TFF_E_INVALID, "robust estimation: fewer correspondences than one sample");   // one-scene variant
+    if (q->n_hyp < 1 || q->n_hyp > (int64_t)INT32_MAX) return fail(TFF_E_INVALID, "robust estimation: n_hyp must be between 1 and 2^31 - 1");
+    if (q->n_cand < 1 || q->n_cand > tff::ROBUST_MAX_CAND) return fail(TFF_E_INVALID, "robust estimation: n_cand must be between 1 and 64");
+    if (q->lo_rounds < 0 || q->lo_rounds > 8) return fail(TFF_E_INVALID, "robust estimation: lo_rounds must be between 0 and 8");
+    if (!(q->threshold > 0.0) || !(q->threshold <= 1.79769313486231570e308)) return fail(TFF_E_INVALID, "robust estimation: the threshold must be a positive finite number");
+    const bool packed = q->n_total != 0;                                     // (nothing packed, no flags: scenes and mask may be null)
+    if ((packed && (!q->scenes || !q->mask)) || !q->calm || !q->Rt2 || !q->Rt3 || !q->T || !q->info || !q->status) return fail(TFF_E_INVALID, "null pointer");
+    if (q->one_scene && q->n_total > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: more than 2^24 correspondences");   // one-scene variant
+    TFF_TRY(ragged_route(c, q->method, route));                              // the refit's refusals: TFF_OPT_ROWS = 0, TFF_OPT_KERNEL = 1
     if (q->S > (int64_t)INT32_MAX / q->n_hyp) return fail(TFF_E_INVALID, "robust estimation: S * n_hyp above 2^31 - 1");
     if (q->S * q->n_cand >= (1L << tff::RETRY_HINT_SHIFT)) return fail(TFF_E_INVALID, "robust estimation: S * n_cand above the ragged call's 2^28 - 1 items");
+    if (!q->rounds) return 0;
+    TFF_TRY(make_round_plan(q->confidence, q->n_hyp, q->first_round, plan));   // its refusals: confidence, first_round, more than 32 rounds
+    if (!q->used) return fail(TFF_E_INVALID, "null pointer");
+    q->plan = plan;
     return 0;
 }
 // the inlier counts of B hypotheses, hypothesis b being g = first + b of the call and belonging to scene g / per
@@ -870,15 +893,25 @@ int launch_count_scenes(tff_ctx* c, const tff::SceneSet& set, const double* Rt2,
     a.live = live;
     return launch(c, msac ? tff::k_inlier_count_scenes_msac : tff::k_inlier_count_scenes, (unsigned)grid, 64 * tff::INLIER_WG_WAVES, ((size_t)36 * rows + (size_t)stage) * sizeof(double), a);
 }
-// device pointers; the lock is held and the context's device current
-int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall& q) {
-    const Method& m = METHODS[q.method];
+// The workspaces of one call, carved by the layouts of robust_layout.h: one chunk of hypotheses, the counts of all of them, the candidates' state
+struct RobustSpace {
+    int64_t G, C, chunk;                     // hypotheses (S * n_hyp) and candidates (S * n_cand) of the call; rows of a chunk
+    double* h_pose; double* h_calm; int32_t* h_status; int32_t* h_idx;       // the chunk (h_calm: null with a shared CalM) ...
+    int32_t* dense; unsigned long long* best; int32_t* live;                 // ... and the rounds' state (the adaptive call)
+    int32_t* counts;                         // G
+    tff::ScenesState st;                     // the candidates; what the host clears or hands to a kernel as an output, writable: ...
+    unsigned long long* sel; uint8_t* masks; int32_t* mask_cnt;              // ... the keys, the K flags per correspondence, their row sums; and ...
+    int32_t* c_idx; double* c_calm;          // ... their sample indices and CalM copies (null with a shared CalM)
+    int32_t* g_ends;                         // the pool tables of a guided call
+};
+// Every reservation of the call, before anything of it is on the stream (DevBuf::reserve frees and allocates, which synchronises the device: none may
+// happen between two launches), and the pointers.  The refit's own workspaces stay with launch_ragged.
+int reserve_robust(tff_ctx* c, const ScenesCall& q, const tff::SceneSet& set, RobustSpace* w) {
     const int K = q.n_cand, n = q.n_sample;
-    const int64_t S = q.S, G = S * q.n_hyp, C = S * K;
-    const tff::SceneSet set{q.scenes, (const long*)q.offsets, (long)S, (long)q.n_total, q.ns_max, n, q.calm, (long)q.calm_stride};
+    const int64_t S = q.S, G = q.n_total ? S * q.n_hyp : 0, C = S * K;       // (without a correspondence nothing is drawn: no chunk, no counts)
     // one chunk of hypotheses: the fixed call cuts g = s * n_hyp + h, the adaptive call the rows of a round (its longest round sizes the chunk)
     int64_t rows_max = G;
-    if (q.plan) {
+    if (q.plan && G) {
         rows_max = 0;
         for (int r = 0; r < q.plan->rounds; ++r) {
             const int64_t len = q.plan->ends[r] - (r ? q.plan->ends[r - 1] : 0);
@@ -888,98 +921,85 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     const int64_t chunk = rows_max < tff::ROBUST_CHUNK ? rows_max : tff::ROBUST_CHUNK;
     // one CalM per scene: every row gets a copy of its scene's for the pose kernels (stride 27).  A shared CalM goes to them as it is (stride 0): no copy is carved or written
     const size_t copies = q.calm_stride ? 27 * sizeof(double) : 0;
-    const size_t hyp_bytes = align256((size_t)chunk * 51 * sizeof(double)) + align256((size_t)chunk * copies) +
-                             align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)chunk * n * sizeof(int32_t));
-    // ... and behind it, for the adaptive call: the round's dense counts | best (S x 8) | live (S x 4)
-    const size_t round_bytes = q.plan ? align256((size_t)chunk * sizeof(int32_t)) + align256((size_t)S * 8) + align256((size_t)S * 4) : 0;
-    if (q.plan) {                                                            // every workspace of the call before its first launch: none grows between two rounds
-        TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
-        TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
-        void* before = c->retry.p;                                           // (the row kernels' retry list, retry_list_begin: sized by the largest chunk)
-        TFF_TRY(c->retry.reserve(((size_t)chunk + 2) * sizeof(int32_t)));
-        if (c->retry.p != before) { TFF_HIP(hipMemsetAsync(c->retry.p, 0, 2 * sizeof(int32_t), c->stream)); c->retry_parity = 0; }
-    }
-    if (q.order) {                                                           // the pool tables' workspace, before anything of this call is on the stream
-        TFF_TRY(c->guided_ends.reserve((size_t)(q.n_total ? q.n_total : 1) * sizeof(int32_t)));
-        if (!q.plan && q.used) TFF_HIP(hipMemsetD32Async((hipDeviceptr_t)q.used, (int)q.n_hyp, (size_t)S, c->stream));   // a fixed n_hyp: used[s] = n_hyp
-    }
-    int32_t* g_ends = (int32_t*)c->guided_ends.p;
+    const tff::ChunkLayout h = tff::chunk_layout(chunk, S, n, copies, q.plan != nullptr);
+    const tff::CandLayout k = tff::cand_layout(C, K, n, q.n_total, copies);
+    TFF_TRY(c->robust_hyp.reserve(h.total));
+    TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
+    TFF_TRY(c->robust_cand.reserve(k.total));
+    if (q.order) TFF_TRY(c->guided_ends.reserve((size_t)(q.n_total ? q.n_total : 1) * sizeof(int32_t)));
+    TFF_TRY(retry_list_reserve(c, chunk > C ? chunk : C));                   // the largest sampled pose launch: a chunk, or the candidates' re-draw
+    w->G = G; w->C = C; w->chunk = chunk;
+    char* hp = (char*)c->robust_hyp.p;
+    w->h_pose = (double*)(hp + h.pose); w->h_calm = copies ? (double*)(hp + h.calm) : nullptr;
+    w->h_status = (int32_t*)(hp + h.status); w->h_idx = (int32_t*)(hp + h.idx);
+    w->dense = (int32_t*)(hp + h.dense); w->best = (unsigned long long*)(hp + h.best); w->live = (int32_t*)(hp + h.live);
+    w->counts = (int32_t*)c->robust_counts.p;
+    w->g_ends = (int32_t*)c->guided_ends.p;
+    char* cp = (char*)c->robust_cand.p;
+    int32_t* ints = (int32_t*)(cp + k.ints);
+    tff::RobustState& s = w->st.s;
+    w->st.q = set; w->st.K = K; w->st.cap = (long)K * q.n_total;
+    w->sel = (unsigned long long*)(cp + k.sel); w->masks = (uint8_t*)(cp + k.mask); w->mask_cnt = ints + 6 * C;
+    s.sel = w->sel; s.K = C;
+    s.cnt = ints; s.seed_idx = ints + C; s.nref = ints + 2 * C; s.status = ints + 3 * C; s.ref_status = ints + 4 * C; s.ref_cnt = ints + 5 * C;
+    s.mask_cnt = w->mask_cnt;
+    s.pose = (double*)(cp + k.pose); s.ref_pose = (double*)(cp + k.ref);
+    s.offsets = (long*)(cp + k.off);
+    s.mask = w->masks;
+    s.packed = (double*)(cp + k.pack);
+    w->c_idx = (int32_t*)(cp + k.idx);
+    w->c_calm = copies ? (double*)(cp + k.calm) : nullptr;
+    return 0;
+}
+// device pointers; the lock is held and the context's device current
+int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall& q) {
+    const Method& m = METHODS[q.method];
+    const int K = q.n_cand, n = q.n_sample;
+    const int64_t S = q.S;
+    const tff::SceneSet set{q.scenes, (const long*)q.offsets, (long)S, (long)q.n_total, q.ns_max, n, q.calm, (long)q.calm_stride};
+    RobustSpace w{};
+    TFF_TRY(reserve_robust(c, q, set, &w));
+    const int64_t G = w.G, C = w.C, chunk = w.chunk;
+    tff::RobustState& s = w.st.s;
     // the sampler of the call: k_scenes_sample, or its guided variant over the pool tables (robust_guided_kernel.h)
     auto sample = [&](const tff::ScenesSampleArgs& a) {
         const unsigned grid = (unsigned)((a.B + 255) / 256);
         if (!q.order) return launch(c, tff::k_scenes_sample, grid, 256, 0, a);
-        return launch(c, tff::k_scenes_sample_guided, grid, 256, 0, tff::ScenesSampleGuidedArgs{a, g_ends, q.order});
+        return launch(c, tff::k_scenes_sample_guided, grid, 256, 0, tff::ScenesSampleGuidedArgs{a, w.g_ends, q.order});
     };
-    if (q.n_total) TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
-    // the candidates: keys | poses | refits | offsets | seven int arrays of C | sample indices | CalM per candidate (per-scene CalM only) | flags | the packed refit batch
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    const size_t o_sel = carve((size_t)C * 8), o_pose = carve((size_t)C * 51 * 8), o_ref = carve((size_t)C * 51 * 8), o_off = carve((size_t)(C + 1) * 8),
-                 o_int = carve((size_t)C * 7 * 4), o_idx = carve((size_t)C * n * 4), o_calm = carve((size_t)C * copies),
-                 o_mask = carve((size_t)K * q.n_total), o_pack = carve((size_t)K * q.n_total * 6 * 8);
-    TFF_TRY(c->robust_cand.reserve(off));
-    char* cp = (char*)c->robust_cand.p;
-    unsigned long long* sel = (unsigned long long*)(cp + o_sel);
-    int32_t* ints = (int32_t*)(cp + o_int);
-    tff::ScenesState st{};
-    tff::RobustState& s = st.s;
-    st.q = set; st.K = K; st.cap = (long)K * q.n_total;
-    s.sel = sel; s.K = C;
-    s.cnt = ints; s.seed_idx = ints + C; s.nref = ints + 2 * C; s.status = ints + 3 * C; s.ref_status = ints + 4 * C; s.ref_cnt = ints + 5 * C;
-    int32_t* mask_cnt = ints + 6 * C;
-    s.mask_cnt = mask_cnt;
-    s.pose = (double*)(cp + o_pose); s.ref_pose = (double*)(cp + o_ref);
-    s.offsets = (long*)(cp + o_off);
-    uint8_t* masks = (uint8_t*)(cp + o_mask);
-    s.mask = masks;
-    s.packed = (double*)(cp + o_pack);
-    int32_t* c_idx = (int32_t*)(cp + o_idx);
-    double* c_calm = copies ? (double*)(cp + o_calm) : nullptr;
-    const tff::ScenesFinishArgs fin{st, q.Rt2, q.Rt3, q.T, q.info, q.status};
-    if (q.n_total == 0) {                                                    // no scene can be valid, and the pose kernels must not gather from an empty array
-        if (q.plan) TFF_HIP(hipMemsetAsync(q.used, 0, (size_t)S * sizeof(int32_t), c->stream));
-        return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
-    }
-    // 0. guided sampling only: every scene's pool table, one workgroup per scene
-    if (q.order)
-        TFF_TRY(launch(c, tff::k_guided_ends, (unsigned)(S < 65536 ? S : 65536), tff::GUIDED_ENDS_THREADS, 0, tff::GuidedEndsArgs{set, (long)q.growth, n, g_ends}));
-
-    // one chunk of hypotheses: poses (51 doubles) | CalM (27, per-scene CalM only) | status | sample indices
-    TFF_TRY(c->robust_hyp.reserve(hyp_bytes + round_bytes));
-    TFF_TRY(c->robust_counts.reserve((size_t)G * sizeof(int32_t)));
-    char* hp = (char*)c->robust_hyp.p;
-    double* h_pose = (double*)hp;                hp += align256((size_t)chunk * 51 * sizeof(double));
-    double* h_calm = copies ? (double*)hp : nullptr;   hp += align256((size_t)chunk * copies);
-    int32_t* h_status = (int32_t*)hp;            hp += align256((size_t)chunk * sizeof(int32_t));
-    int32_t* h_idx = (int32_t*)hp;               hp += align256((size_t)chunk * n * sizeof(int32_t));
-    int32_t* counts = (int32_t*)c->robust_counts.p;
-
     // the method's *_pose_sampled_dev on the packed array: global indices, one CalM per row (`calm`) or the shared one
     auto sampled = [&](const int32_t* idx, const double* calm, int64_t B, double* pose, int32_t* status) {
         PoseCall p{q.scenes, calm ? calm : q.calm, q.calm_stride, B, n, pose, pose + B * 12, pose + B * 24, nullptr, nullptr, status, nullptr};
         p.sample_idx = idx; p.sample_ns = (int32_t)q.n_total;
         return m.launch(c, p);
     };
+    const tff::ScenesFinishArgs fin{w.st, q.Rt2, q.Rt3, q.T, q.info, q.status};
+    if (q.order && !q.plan && q.used) TFF_HIP(hipMemsetD32Async((hipDeviceptr_t)q.used, (int)q.n_hyp, (size_t)S, c->stream));   // guided, a fixed n_hyp: used[s] = n_hyp
+    if (q.n_total == 0) {                                                    // no scene can be valid, and the pose kernels must not gather from an empty array
+        if (q.plan) TFF_HIP(hipMemsetAsync(q.used, 0, (size_t)S * sizeof(int32_t), c->stream));
+        return launch(c, tff::k_scenes_finish, (unsigned)S, 64, 0, fin);
+    }
+    TFF_HIP(hipMemsetAsync(q.mask, 0, (size_t)q.n_total, c->stream));
+    // 0. guided sampling only: every scene's pool table, one workgroup per scene
+    if (q.order)
+        TFF_TRY(launch(c, tff::k_guided_ends, (unsigned)(S < 65536 ? S : 65536), tff::GUIDED_ENDS_THREADS, 0, tff::GuidedEndsArgs{set, (long)q.growth, n, w.g_ends}));
     // 1a. the adaptive call: round r draws the hypotheses [e_prev, e_end) of the scenes that are still live, chunk by chunk over the round's rows
     //     g' = s * len + i; the counts land where the fixed call puts them (stride n_hyp, -1 where nothing was drawn), the rule closes the round
     if (q.plan) {
-        int32_t* dense = (int32_t*)hp;               hp += align256((size_t)chunk * sizeof(int32_t));
-        unsigned long long* best = (unsigned long long*)hp;   hp += align256((size_t)S * 8);
-        int32_t* live = (int32_t*)hp;
-        const tff::RoundState rs{set, live, best, q.used};
+        const tff::RoundState rs{set, w.live, w.best, q.used};
         const unsigned sgrid = (unsigned)((S + 255) / 256);
-        TFF_HIP(hipMemsetAsync(counts, 0xFF, (size_t)G * sizeof(int32_t), c->stream));
+        TFF_HIP(hipMemsetAsync(w.counts, 0xFF, (size_t)G * sizeof(int32_t), c->stream));
         TFF_TRY(launch(c, tff::k_round_init, sgrid, 256, 0, rs));
         int64_t e_prev = 0;
         for (int r = 0; r < q.plan->rounds; ++r) {
             const int64_t e_end = q.plan->ends[r], len = e_end - e_prev, Gr = S * len;
             for (int64_t first = 0; first < Gr; first += chunk) {
                 const int64_t B = Gr - first < chunk ? Gr - first : chunk;
-                TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)len, n, h_idx, h_calm, (long)e_prev, live}));
-                TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
-                TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, len, q.threshold, dense, live));
+                TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)len, n, w.h_idx, w.h_calm, (long)e_prev, w.live}));
+                TFF_TRY(sampled(w.h_idx, w.h_calm, B, w.h_pose, w.h_status));
+                TFF_TRY(launch_count_scenes(c, set, w.h_pose, w.h_pose + B * 12, first, B, len, q.threshold, w.dense, w.live));
                 TFF_TRY(launch(c, tff::k_round_scatter, (unsigned)((B + 255) / 256), 256, 0,
-                               tff::RoundScatterArgs{dense, h_status, (long)first, (long)B, (long)len, (long)e_prev, (long)q.n_hyp, live, best, counts}));
+                               tff::RoundScatterArgs{w.dense, w.h_status, (long)first, (long)B, (long)len, (long)e_prev, (long)q.n_hyp, w.live, w.best, w.counts}));
             }
             TFF_TRY(launch(c, tff::k_round_close, sgrid, 256, 0,
                            tff::RoundCloseArgs{rs, (long)e_end, q.plan->qmin[r], n, c->score == 1 ? TFF_SCORE_UNITS : 1}));
@@ -989,38 +1009,38 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
     // 1. hypotheses and their counts, chunk by chunk over g = s * n_hyp + h
     for (int64_t first = 0; !q.plan && first < G; first += chunk) {
         const int64_t B = G - first < chunk ? G - first : chunk;
-        TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, h_idx, h_calm}));
-        TFF_TRY(sampled(h_idx, h_calm, B, h_pose, h_status));
+        TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, (long)first, nullptr, (long)B, (long)q.n_hyp, n, w.h_idx, w.h_calm}));
+        TFF_TRY(sampled(w.h_idx, w.h_calm, B, w.h_pose, w.h_status));
         // The one branch on the form of the call: without offsets (tff_robust_pose_dev: one valid scene [0, n_total), shared CalM) the hypotheses are counted
         // by the one-scene launcher, whose one-wavefront-per-hypothesis route serves a few thousand hypotheses better than sixteen per workgroup.  Measured
         // (DESIGN.md 3.4): 0.05 ms per 1 000-hypothesis call, and the 1 M-hypothesis LinearF call back under the bar it missed by 0.16 % without it.  The
         // integers are those of k_inlier_count_scenes (count_if_inlier / score_if_inlier in both; tests/test_gpu_robust.py, test_gpu_score.py).
         // tff_robust_pose_host arrives with the offsets {0, Ns} and takes the other route, on purpose: it is keyed on what the kernels are given, the call
         // is dominated by its copies and its synchronisation, and a second key would be a second special case.  The refit counts always go the scenes route.
-        if (!q.offsets) TFF_TRY(launch_inlier_count(c, q.scenes, (int32_t)q.n_total, q.calm, h_pose, h_pose + B * 12, B, q.threshold, counts + first, nullptr));
-        else TFF_TRY(launch_count_scenes(c, set, h_pose, h_pose + B * 12, first, B, q.n_hyp, q.threshold, counts + first));
-        TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{counts + first, h_status, (long)B}));
+        if (!q.offsets) TFF_TRY(launch_inlier_count(c, q.scenes, (int32_t)q.n_total, q.calm, w.h_pose, w.h_pose + B * 12, B, q.threshold, w.counts + first, nullptr));
+        else TFF_TRY(launch_count_scenes(c, set, w.h_pose, w.h_pose + B * 12, first, B, q.n_hyp, q.threshold, w.counts + first));
+        TFF_TRY(launch(c, tff::k_robust_mark, (unsigned)((B + 255) / 256), 256, 0, tff::RobustMarkArgs{w.counts + first, w.h_status, (long)B}));
     }
     // 2. per scene the K best successes, then their poses again from their indices
-    TFF_HIP(hipMemsetAsync(sel, 0, (size_t)C * 8, c->stream));
+    TFF_HIP(hipMemsetAsync(w.sel, 0, (size_t)C * 8, c->stream));
     long topk_blocks = (q.n_hyp + tff::ROBUST_TOPK_THREADS - 1) / tff::ROBUST_TOPK_THREADS;
     if (topk_blocks > 1024) topk_blocks = 1024;
     for (int64_t s0 = 0; s0 < S; s0 += 65535) {                              // (gridDim.y)
         const unsigned sy = (unsigned)(S - s0 < 65535 ? S - s0 : 65535);
         for (int r = 0; r < K; ++r)
             TFF_TRY(launch(c, tff::k_robust_topk, dim3((unsigned)topk_blocks, sy), tff::ROBUST_TOPK_THREADS, 0,
-                           tff::RobustTopkArgs{counts + s0 * q.n_hyp, (long)q.n_hyp, sel + s0 * K, r, K}));
+                           tff::RobustTopkArgs{w.counts + s0 * q.n_hyp, (long)q.n_hyp, w.sel + s0 * K, r, K}));
     }
-    TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, 0, sel, (long)C, (long)K, n, c_idx, c_calm}));
-    TFF_TRY(sampled(c_idx, c_calm, C, s.pose, s.status));
+    TFF_TRY(sample(tff::ScenesSampleArgs{set, (unsigned long long)q.seed, 0, w.sel, (long)C, (long)K, n, w.c_idx, w.c_calm}));
+    TFF_TRY(sampled(w.c_idx, w.c_calm, C, s.pose, s.status));
     TFF_TRY(launch(c, tff::k_robust_seed, (unsigned)((C + 63) / 64), 64, 0, s));
     // 3. local optimisation, the candidates of all scenes at once: flags -> packed inliers -> one ragged refit -> counts -> adopt
     for (int round = 0; round < q.lo_rounds; ++round) {
         TFF_TRY(launch(c, tff::k_scenes_mask, tff::pose_grid(C), 64, 0,
-                       tff::ScenesMaskArgs{set, s.pose, s.pose + C * 12, (long)C, (long)K, q.threshold, masks, mask_cnt, s.cnt, nullptr}));
-        TFF_TRY(launch(c, tff::k_scenes_offsets, 1, tff::SCENES_SCAN_THREADS, 0, st));
-        TFF_TRY(launch(c, tff::k_scenes_compact, (unsigned)C, tff::ROBUST_COMPACT_THREADS, 0, st));
-        PoseCall p{s.packed, c_calm ? c_calm : q.calm, q.calm_stride, C, q.ns_max, s.ref_pose, s.ref_pose + C * 12, s.ref_pose + C * 24, nullptr, nullptr, s.ref_status, nullptr};
+                       tff::ScenesMaskArgs{set, s.pose, s.pose + C * 12, (long)C, (long)K, q.threshold, w.masks, w.mask_cnt, s.cnt, nullptr}));
+        TFF_TRY(launch(c, tff::k_scenes_offsets, 1, tff::SCENES_SCAN_THREADS, 0, w.st));
+        TFF_TRY(launch(c, tff::k_scenes_compact, (unsigned)C, tff::ROBUST_COMPACT_THREADS, 0, w.st));
+        PoseCall p{s.packed, w.c_calm ? w.c_calm : q.calm, q.calm_stride, C, q.ns_max, s.ref_pose, s.ref_pose + C * 12, s.ref_pose + C * 24, nullptr, nullptr, s.ref_status, nullptr};
         p.offsets = (const int64_t*)s.offsets;
         TFF_TRY(launch_ragged(c, route, p));
         TFF_TRY(launch_count_scenes(c, set, s.ref_pose, s.ref_pose + C * 12, 0, C, K, q.threshold, s.ref_cnt));
@@ -1033,8 +1053,8 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
                       tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, nullptr, nullptr, q.status});
     // MSAC: info[0] holds the winner's score; the row sums of the returned flags replace it (mask_cnt is free again: C >= S ints)
     TFF_TRY(launch(c, tff::k_scenes_mask, tff::pose_grid(S), 64, 0,
-                   tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, mask_cnt, nullptr, q.status}));
-    return launch(c, tff::k_scenes_info, (unsigned)((S + 255) / 256), 256, 0, tff::ScenesInfoArgs{mask_cnt, q.status, q.info, (long)S});
+                   tff::ScenesMaskArgs{set, q.Rt2, q.Rt3, (long)S, 1, q.threshold, q.mask, w.mask_cnt, nullptr, q.status}));
+    return launch(c, tff::k_scenes_info, (unsigned)((S + 255) / 256), 256, 0, tff::ScenesInfoArgs{w.mask_cnt, q.status, q.info, (long)S});
 }
 
 }  // namespace
@@ -1238,112 +1258,89 @@ int tff_inlier_mask_batch_dev(tff_ctx* c, const double* scene, int32_t Ns, const
                      });
 }
 
-// The one-scene forms: their own refusals (check_robust with the real Ns: a scene smaller than a sample is TFF_E_INVALID here, not a per-scene status),
-// then the chain for S = 1.  The _dev form is given no offsets: a null SceneSet::offsets is the one scene [0, Ns)
+// The two drivers of every robust entry point.  Device pointers: the checks, the rounds, an empty list (only now: S == 0 is no licence for bad arguments),
+// the chain.  No synchronisation.
+static int robust_dev(tff_ctx* c, ScenesCall q) {
+    const RaggedRoute* route;
+    RoundPlan plan;
+    TFF_TRY(check_scenes(c, &q, false, &plan, &route));
+    if (q.S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    return launch_robust_scenes(c, *route, q);
+}
+// Host pointers: the checks of robust_dev, a list's offsets among them (n_total and ns_max come from them); H2D, its chain, D2H, one synchronisation
+static int robust_host(tff_ctx* c, ScenesCall h) {
+    const int64_t S = h.S;
+    const RaggedRoute* route;
+    RoundPlan plan;
+    TFF_TRY(check_scenes(c, &h, true, &plan, &route));
+    if (S == 0) return 0;
+    TFF_HIP(hipSetDevice(c->device));
+    const int64_t n_total = h.n_total;
+    const size_t nscene = (size_t)n_total * 6 * sizeof(double), ncal = (size_t)(h.calm_stride ? S : 1) * 27 * sizeof(double), nS = (size_t)S;
+    TFF_TRY(c->in.reserve(nscene ? nscene : 8));
+    TFF_TRY(c->calm.reserve(ncal));
+    TFF_TRY(c->ragged_off.reserve((nS + 1) * sizeof(int64_t)));
+    TFF_TRY(c->out.reserve(nS * 51 * sizeof(double) + (size_t)n_total + 8));
+    TFF_TRY(c->idx.reserve(nS * 6 * sizeof(int32_t)));
+    if (h.order) TFF_TRY(c->guided_order.reserve((size_t)(n_total ? n_total : 1) * sizeof(int32_t)));   // the guided form: the ranking's copy
+    ScenesCall d = h;
+    d.scenes = (const double*)c->in.p; d.calm = (const double*)c->calm.p; d.offsets = (const int64_t*)c->ragged_off.p;
+    d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + nS * 12; d.T = d.Rt3 + nS * 12; d.mask = (uint8_t*)(d.T + nS * 27);
+    d.info = (int32_t*)c->idx.p; d.status = d.info + nS * 4; d.used = d.status + nS;
+    if (nscene) TFF_HIP(hipMemcpyAsync(c->in.p, h.scenes, nscene, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(c->calm.p, h.calm, ncal, hipMemcpyHostToDevice, c->stream));
+    TFF_HIP(hipMemcpyAsync(c->ragged_off.p, h.offsets, (nS + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (h.order) {                                                           // the guided form: the ranking travels like the scenes
+        if (n_total) TFF_HIP(hipMemcpyAsync(c->guided_order.p, h.order, (size_t)n_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        d.order = (const int32_t*)c->guided_order.p;
+        if (!h.plan) d.used = nullptr;                                       // (a fixed n_hyp: the caller's used, if any, is filled on the host, below)
+    }
+    TFF_TRY(launch_robust_scenes(c, *route, d));
+    TFF_HIP(hipMemcpyAsync(h.Rt2, d.Rt2, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(h.Rt3, d.Rt3, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(h.T, d.T, nS * 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_total) TFF_HIP(hipMemcpyAsync(h.mask, d.mask, (size_t)n_total, hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(h.info, d.info, nS * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipMemcpyAsync(h.status, d.status, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (h.plan) TFF_HIP(hipMemcpyAsync(h.used, d.used, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TFF_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+// the one-scene forms: S = 1 with a shared CalM; offsets: none (_dev) or {0, Ns} on the host (_host)
 int tff_robust_pose_dev(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
                         int32_t* status) {
     TFF_ENTER(c);
-    RobustCall q{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_robust(c, &q, &route));
-    TFF_HIP(hipSetDevice(c->device));
-    return launch_robust_scenes(c, *route, ScenesCall{method, scene, nullptr, Ns, Ns, 1, calm, 0, seed, n_hyp, q.n_sample, threshold, n_cand, lo_rounds,
-                                                      Rt2, Rt3, T, mask, info, status});
+    ScenesCall q{method, scene, nullptr, Ns, Ns, 1, calm, 0, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
+    q.one_scene = true;
+    return robust_dev(c, q);
+}
+int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
+                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
+                         int32_t* status) {
+    TFF_ENTER(c);
+    const int64_t offsets[2] = {0, Ns};
+    ScenesCall q{method, scene, offsets, Ns, Ns, 1, calm, 0, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
+    q.one_scene = true;
+    return robust_host(c, q);
 }
 
 int tff_robust_pose_scenes_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max, int64_t S,
                                const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
                                int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
     TFF_ENTER(c);
-    ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
-                 Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_scenes(c, &q, &route));
-    if (S == 0) return 0;
-    TFF_HIP(hipSetDevice(c->device));
-    return launch_robust_scenes(c, *route, q);
-}
-
-// host pointers: the offsets are checked here, n_total and ns_max come from them; H2D, the _dev path, D2H, one synchronisation
-// (the lock is held.  confidence: null for the fixed form; else the adaptive form's, with first_round and used)
-static int robust_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
-                              int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
-                              double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status, const double* confidence,
-                              int32_t first_round, int32_t* used, const int32_t* order = nullptr, int64_t growth = 0) {
-    if (S < 0) return fail(TFF_E_INVALID, "robust estimation: negative number of scenes");
-    if (!scene_offsets) return fail(TFF_E_INVALID, "null offsets");
-    if (scene_offsets[0] < 0) return fail(TFF_E_INVALID, "robust estimation: negative offset");
-    int64_t ns_max = 0;
-    for (int64_t s = 0; s < S; ++s) {
-        const int64_t ns = scene_offsets[s + 1] - scene_offsets[s];
-        if (ns < 0) return fail(TFF_E_INVALID, "robust estimation: decreasing offsets");
-        if (ns > ns_max) ns_max = ns;
-    }
-    const int64_t n_total = scene_offsets[S];
-    if (ns_max > RAGGED_MAX_N) return fail(TFF_E_INVALID, "robust estimation: a scene of more than 2^24 correspondences");
-    ScenesCall h{method, scenes, scene_offsets, n_total, (int32_t)ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
-                 Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_scenes(c, &h, &route));
-    RoundPlan plan;
-    if (confidence) {
-        TFF_TRY(make_round_plan(*confidence, n_hyp, first_round, &plan));
-        if (!used) return fail(TFF_E_INVALID, "null pointer");
-        h.plan = &plan;
-    }
-    if (S == 0) return 0;
-    TFF_HIP(hipSetDevice(c->device));
-    const size_t nscene = (size_t)n_total * 6 * sizeof(double), ncal = (size_t)(calm_stride ? S : 1) * 27 * sizeof(double), nS = (size_t)S;
-    TFF_TRY(c->in.reserve(nscene ? nscene : 8));
-    TFF_TRY(c->calm.reserve(ncal));
-    TFF_TRY(c->ragged_off.reserve((nS + 1) * sizeof(int64_t)));
-    TFF_TRY(c->out.reserve(nS * 51 * sizeof(double) + (size_t)n_total + 8));
-    TFF_TRY(c->idx.reserve(nS * 6 * sizeof(int32_t)));
-    if (order) TFF_TRY(c->guided_order.reserve((size_t)(n_total ? n_total : 1) * sizeof(int32_t)));   // the guided form: the ranking's copy
-    ScenesCall d = h;
-    d.scenes = (const double*)c->in.p; d.calm = (const double*)c->calm.p; d.offsets = (const int64_t*)c->ragged_off.p;
-    d.Rt2 = (double*)c->out.p; d.Rt3 = d.Rt2 + nS * 12; d.T = d.Rt3 + nS * 12; d.mask = (uint8_t*)(d.T + nS * 27);
-    d.info = (int32_t*)c->idx.p; d.status = d.info + nS * 4; d.used = d.status + nS;
-    if (nscene) TFF_HIP(hipMemcpyAsync(c->in.p, scenes, nscene, hipMemcpyHostToDevice, c->stream));
-    TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
-    TFF_HIP(hipMemcpyAsync(c->ragged_off.p, scene_offsets, (nS + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    if (order) {                                                             // the guided form: the ranking travels like the scenes
-        if (n_total) TFF_HIP(hipMemcpyAsync(c->guided_order.p, order, (size_t)n_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        d.order = (const int32_t*)c->guided_order.p; d.growth = growth;
-        if (!confidence) d.used = nullptr;                                   // (a fixed n_hyp: the caller's used, if any, is filled on the host)
-    }
-    TFF_TRY(launch_robust_scenes(c, *route, d));
-    TFF_HIP(hipMemcpyAsync(Rt2, d.Rt2, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(Rt3, d.Rt3, nS * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(T, d.T, nS * 27 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (n_total) TFF_HIP(hipMemcpyAsync(mask, d.mask, (size_t)n_total, hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(info, d.info, nS * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipMemcpyAsync(status, d.status, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (confidence) TFF_HIP(hipMemcpyAsync(used, d.used, nS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TFF_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int tff_robust_pose_host(tff_ctx* c, int32_t method, const double* scene, int32_t Ns, const double* calm, uint64_t seed, int64_t n_hyp, int32_t n_sample,
-                         double threshold, int32_t n_cand, int32_t lo_rounds, double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info,
-                         int32_t* status) {
-    TFF_ENTER(c);
-    RobustCall h{method, scene, Ns, calm, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_robust(c, &h, &route));
-    const int64_t offsets[2] = {0, Ns};
-    return robust_scenes_host(c, method, scene, offsets, 1, calm, 0, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask, info, status,
-                              nullptr, 0, nullptr);
+    return robust_dev(c, ScenesCall{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                                    Rt2, Rt3, T, mask, info, status});
 }
 int tff_robust_pose_scenes_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                                 int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand, int32_t lo_rounds,
                                 double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* status) {
     TFF_ENTER(c);
-    return robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
-                              info, status, nullptr, 0, nullptr);
+    return robust_host(c, ScenesCall{method, scenes, scene_offsets, 0, 0, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                                     Rt2, Rt3, T, mask, info, status});
 }
 
-// the adaptive forms: the fixed forms' checks, then the plan of rounds (its refusals: confidence, first_round, more than 32 rounds) and `used`
 int tff_robust_round_plan(double confidence, int64_t n_hyp, int32_t first_round, int64_t* ends, double* qmin, int32_t* rounds) {
     if (!ends || !qmin || !rounds) return fail(TFF_E_INVALID, "null pointer");
     RoundPlan p;
@@ -1353,6 +1350,8 @@ int tff_robust_round_plan(double confidence, int64_t n_hyp, int32_t first_round,
     return 0;
 }
 
+// the adaptive and the guided forms (include/tftfund_adaptive.h, include/tftfund_guided.h; kernels in robust_guided_kernel.h): the list's record plus the
+// early stop (the guided forms: with a confidence other than 0; 0 is a fixed n_hyp, no rounds) and the ranking
 int tff_robust_pose_scenes_adaptive_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max,
                                         int64_t S, const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold,
                                         int32_t n_cand, int32_t lo_rounds, double confidence, int32_t first_round, double* Rt2, double* Rt3, double* T,
@@ -1360,67 +1359,46 @@ int tff_robust_pose_scenes_adaptive_dev(tff_ctx* c, int32_t method, const double
     TFF_ENTER(c);
     ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
                  Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_scenes(c, &q, &route));
-    RoundPlan plan;
-    TFF_TRY(make_round_plan(confidence, n_hyp, first_round, &plan));
-    if (!used) return fail(TFF_E_INVALID, "null pointer");
-    q.plan = &plan; q.used = used;
-    if (S == 0) return 0;
-    TFF_HIP(hipSetDevice(c->device));
-    return launch_robust_scenes(c, *route, q);
+    q.rounds = true; q.confidence = confidence; q.first_round = first_round; q.used = used;
+    return robust_dev(c, q);
 }
-
 int tff_robust_pose_scenes_adaptive_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                                          int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
                                          int32_t lo_rounds, double confidence, int32_t first_round, double* Rt2, double* Rt3, double* T, uint8_t* mask,
                                          int32_t* info, int32_t* used, int32_t* status) {
     TFF_ENTER(c);
-    return robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
-                              info, status, &confidence, first_round, used);
-}
-
-// ---- quality-guided sampling (include/tftfund_guided.h; kernels in robust_guided_kernel.h) -----------------------------------------------------------
-// the two arguments every guided entry point adds, refused first
-static int check_guided(const int32_t* order, int64_t growth) {
-    if (!order) return fail(TFF_E_INVALID, "guided sampling: null order");
-    if (growth < 1 || growth > (int64_t)tff::GUIDED_MAX_GROWTH) return fail(TFF_E_INVALID, "guided sampling: growth must be between 1 and 2^31 - 2^25");
-    return 0;
+    ScenesCall q{method, scenes, scene_offsets, 0, 0, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    q.rounds = true; q.confidence = confidence; q.first_round = first_round; q.used = used;
+    return robust_host(c, q);
 }
 int tff_robust_pose_scenes_guided_dev(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t n_total, int32_t ns_max,
                                       int64_t S, const double* calm, int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold,
                                       int32_t n_cand, int32_t lo_rounds, double confidence, int32_t first_round, const int32_t* order, int64_t growth,
                                       double* Rt2, double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* used, int32_t* status) {
     TFF_ENTER(c);
-    TFF_TRY(check_guided(order, growth));
     ScenesCall q{method, scenes, scene_offsets, n_total, ns_max, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
                  Rt2, Rt3, T, mask, info, status};
-    const RaggedRoute* route;
-    TFF_TRY(check_scenes(c, &q, &route));
-    RoundPlan plan;
-    if (confidence != 0.0) {                                                 // 0: a fixed n_hyp, no rounds; anything else is the adaptive call's confidence
-        TFF_TRY(make_round_plan(confidence, n_hyp, first_round, &plan));
-        if (!used) return fail(TFF_E_INVALID, "null pointer");
-        q.plan = &plan;
-    }
-    q.used = used;                                                           // (without a plan: null, or filled with n_hyp by launch_robust_scenes)
-    q.order = order; q.growth = growth;
-    if (S == 0) return 0;
-    TFF_HIP(hipSetDevice(c->device));
-    return launch_robust_scenes(c, *route, q);
+    q.rounds = confidence != 0.0; q.confidence = confidence; q.first_round = first_round;
+    q.used = used;                                                           // (without rounds: null, or filled with n_hyp by launch_robust_scenes)
+    q.guided = true; q.order = order; q.growth = growth;
+    return robust_dev(c, q);
 }
 int tff_robust_pose_scenes_guided_host(tff_ctx* c, int32_t method, const double* scenes, const int64_t* scene_offsets, int64_t S, const double* calm,
                                        int64_t calm_stride, uint64_t seed, int64_t n_hyp, int32_t n_sample, double threshold, int32_t n_cand,
                                        int32_t lo_rounds, double confidence, int32_t first_round, const int32_t* order, int64_t growth, double* Rt2,
                                        double* Rt3, double* T, uint8_t* mask, int32_t* info, int32_t* used, int32_t* status) {
     TFF_ENTER(c);
-    TFF_TRY(check_guided(order, growth));
-    TFF_TRY(robust_scenes_host(c, method, scenes, scene_offsets, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds, Rt2, Rt3, T, mask,
-                               info, status, confidence != 0.0 ? &confidence : nullptr, first_round, used, order, growth));
-    if (confidence == 0.0 && used)
+    ScenesCall q{method, scenes, scene_offsets, 0, 0, S, calm, calm_stride, seed, n_hyp, n_sample, threshold, n_cand, lo_rounds,
+                 Rt2, Rt3, T, mask, info, status};
+    q.rounds = confidence != 0.0; q.confidence = confidence; q.first_round = first_round; q.used = used;
+    q.guided = true; q.order = order; q.growth = growth;
+    TFF_TRY(robust_host(c, q));
+    if (confidence == 0.0 && used)                                           // a fixed n_hyp: documented as used[s] = n_hyp, and the call had no device copy of it
         for (int64_t s = 0; s < S; ++s) used[s] = (int32_t)n_hyp;
     return 0;
 }
+// the guided one-scene building block (include/tftfund_guided.h)
 int tff_sample_indices_guided_dev(tff_ctx* c, uint64_t seed, int64_t first, int64_t B, int32_t n, int32_t Ns, const int32_t* order, int64_t growth,
                                   int32_t* sample_idx) {
     TFF_ENTER(c);

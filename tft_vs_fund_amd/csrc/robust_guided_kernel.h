@@ -4,7 +4,7 @@
 // (seed, h, m, N, growth, the scene's ranking) and every bitwise contract of the robust calls holds as it does for the uniform sampler.
 //
 //   k_guided_ends            per scene the table ends[m .. N]: hypothesis t = h + 1 draws from the smallest pool n with ends[n] >= t
-//   k_scenes_sample_guided   k_scenes_sample with the guided draw: rows of a chunk or round, or the re-draw of the candidates from their keys
+//   k_scenes_sample_guided   scenes_sample_row, k_scenes_sample's body, with the guided draw: rows of a chunk or round, or the re-draw of the candidates from their keys
 //   k_sample_indices_guided  the one-scene building block
 //
 // The table is packed like the scenes: slot offsets[s] + n - 1 holds ends[n] of scene s (slots below m - 1 hold 0), n_total int32 in all.
@@ -111,20 +111,9 @@ struct ScenesSampleGuidedArgs {
     const int* order;        // n_total: per scene its ranking, best first, as local indices
 };
 __global__ void __launch_bounds__(256) k_scenes_sample_guided(const ScenesSampleGuidedArgs ga) {
-    const ScenesSampleArgs& a = ga.a;
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
-    const long g = a.first + b;
-    const long s = g / a.per;
-    const unsigned long long h = a.keys ? (unsigned long long)robust_key_index(a.keys[b]) : (unsigned long long)(a.hyp_base + (g - s * a.per));
-    long o; int ns;
-    const bool ok = scene_range(a.q, s, &o, &ns) == ST_OK && !(a.live && a.live[s] == 0);
-    int* out = a.out + b * a.n;
-    if (ok) guided_draw(a.seed + (unsigned long long)s, h, a.n, ns, ga.ends + o, ga.order + o, (int)o, out);
-    else for (int i = 0; i < a.n; ++i) out[i] = -1;
-    if (!a.calm_out) return;
-    const double* calm = a.q.calm + s * a.q.calm_stride;
-    for (int e = 0; e < 27; ++e) a.calm_out[b * 27 + e] = calm[e];
+    scenes_sample_row(ga.a, [&](unsigned long long seed, unsigned long long h, int ns, long o, int* out) {
+        guided_draw(seed, h, ga.a.n, ns, ga.ends + o, ga.order + o, (int)o, out);
+    });
 }
 
 struct SampleGuidedArgs {

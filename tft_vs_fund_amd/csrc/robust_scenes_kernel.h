@@ -54,7 +54,10 @@ struct ScenesSampleArgs {
     long hyp_base;           // a round of the adaptive call (per = the round's length): the row's hypothesis is hyp_base + g % per; 0 otherwise
     const int* live;         // null, or S: a scene with live[s] == 0 gets indices -1, like an invalid one
 };
-__global__ void __launch_bounds__(256) k_scenes_sample(const ScenesSampleArgs a) {
+// One row of a scene sampler (k_scenes_sample; k_scenes_sample_guided in robust_guided_kernel.h): the row's (s, h), its scene's validity and liveness,
+// the n indices by draw(seed + s, h, ns, o, out) or a row of -1, the CalM copy
+template <class Draw>
+__device__ __forceinline__ void scenes_sample_row(const ScenesSampleArgs& a, const Draw draw) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
     const long g = a.first + b;
@@ -63,11 +66,14 @@ __global__ void __launch_bounds__(256) k_scenes_sample(const ScenesSampleArgs a)
     long o; int ns;
     const bool ok = scene_range(a.q, s, &o, &ns) == ST_OK && !(a.live && a.live[s] == 0);
     int* out = a.out + b * a.n;
-    if (ok) sample_draw(a.seed + (unsigned long long)s, h, a.n, ns, (int)o, out);
+    if (ok) draw(a.seed + (unsigned long long)s, h, ns, o, out);
     else for (int i = 0; i < a.n; ++i) out[i] = -1;
     if (!a.calm_out) return;
     const double* calm = a.q.calm + s * a.q.calm_stride;
     for (int e = 0; e < 27; ++e) a.calm_out[b * 27 + e] = calm[e];
+}
+__global__ void __launch_bounds__(256) k_scenes_sample(const ScenesSampleArgs a) {
+    scenes_sample_row(a, [&](unsigned long long seed, unsigned long long h, int ns, long o, int* out) { sample_draw(seed, h, a.n, ns, (int)o, out); });
 }
 
 // ---- inlier counts: hypotheses of many scenes -------------------------------------------------------------------------------------------------

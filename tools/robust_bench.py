@@ -3,7 +3,8 @@
 Robust pose estimation against the composition it replaces, on the config-4 scene (400 correspondences at 0.5 px noise, 100 of them displaced
 by U(20, 80) px in views 2 and 3):
 
-  (a) Context.robust_pose: device-side sampler, hypotheses, counts, top-K selection, K refits per round -- one call, no host synchronisation;
+  (a) Context.robust_pose (tff_robust_pose_dev: capi.hip::robust_dev, the scene-list chain with S = 1): device-side sampler, hypotheses, counts,
+      top-K selection, K refits per round -- one call, no host synchronisation;
   (b) what tools/config4_ransac.py times: torch sampler (rand + argsort) + pose_sampled + inlier_count + argmax.
 
 Both at the same threshold, alternated in one process, each the median of `--reps` repetitions after a warm-up, timed with the host clock around
