@@ -60,14 +60,15 @@ __device__ __forceinline__ void rows_distances_moments_f(const RowSrc& s, const 
         if (p == 3 * v + 1) { nrm[3 * v + 1] = -r2c * c[2 * v] / norm0; nrm2[3 * v + 1] = 0.0; }          // :37
         if (p == 3 * v + 2) { nrm[3 * v + 2] = -r2c * c[2 * v + 1] / norm0; nrm2[3 * v + 2] = 0.0; }
     }
+    const bool up8 = (p & 8) != 0, up4 = (p & 4) != 0, up2 = (p & 2) != 0, up1 = (p & 1) != 0;   // (once for the 75 steps)
 #pragma unroll
-    for (int i = 0; i < 40; ++i) acc[i] = halve_sum<8>(acc[i], acc[i + 40]);
+    for (int i = 0; i < 40; ++i) acc[i] = halve_sum<8>(acc[i], acc[i + 40], up8);
 #pragma unroll
-    for (int i = 0; i < 20; ++i) acc[i] = halve_sum<4>(acc[i], acc[i + 20]);
+    for (int i = 0; i < 20; ++i) acc[i] = halve_sum<4>(acc[i], acc[i + 20], up4);
 #pragma unroll
-    for (int i = 0; i < 10; ++i) acc[i] = halve_sum<2>(acc[i], acc[i + 10]);
+    for (int i = 0; i < 10; ++i) acc[i] = halve_sum<2>(acc[i], acc[i + 10], up2);
 #pragma unroll
-    for (int i = 0; i < 5; ++i) acc[i] = halve_sum<1>(acc[i], acc[i + 5]);
+    for (int i = 0; i < 5; ++i) acc[i] = halve_sum<1>(acc[i], acc[i + 5], up1);
     const int base = 5 * (p & 1) + 10 * ((p >> 1) & 1) + 20 * ((p >> 2) & 1) + 40 * ((p >> 3) & 1);
 #pragma unroll
     for (int i = 0; i < 5; ++i) {

@@ -21,6 +21,7 @@
 #include "tft_kernel.h"
 #include "tft_moments_kernel.h"
 #include <rows_target.h>
+#include <regs_target.h>
 
 namespace tff {
 
@@ -109,9 +110,10 @@ __device__ __forceinline__ void rows_centroids(const RowSrc& s, const int N, dou
         for (int u = 0; u < 4; ++u) { const int i = i0 + ROWL * u + p; q[u] = rows_load(s, (i < N) ? i : 0); }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const bool have = i0 + ROWL * u + p < N;
+            if (i0 + ROWL * u + p < N) {                                     // (sm[k] is never -0.0: skipping the addition of +0.0 leaves the same bits)
 #pragma unroll
-            for (int k = 0; k < 6; ++k) sm[k] += have ? q[u].v[k] : 0.0;
+                for (int k = 0; k < 6; ++k) sm[k] += q[u].v[k];
+            }
         }
     }
 #pragma unroll
@@ -132,7 +134,7 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
     const bool odd = (p & 1) != 0;
     double acc[48];
 #pragma unroll
-    for (int k = 0; k < 48; ++k) acc[k] = 0.0;
+    for (int k = 0; k < 48; ++k) acc[k] = zero_f64();                        // (one 64-bit move each: regs_target.h)
     double dA = 0.0, dB = 0.0;
     // (the loads of trips t + 1 and t + 2 are in flight while trip t is consumed: a trip issues ~80 fp64 instructions, an L2 / MALL round trip
     // lasts five times that, and the other wavefront of the SIMD is in the same pass more often than not)
@@ -185,19 +187,18 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
         nr[3 * v + 1] = -r2c * c[2 * v] / norm0;                             // :37
         nr[3 * v + 2] = -r2c * c[2 * v + 1] / norm0;
     }
-    if (p < 9) {
-        double mine = nr[0];
+    if (p == 0) {                                                            // (every lane of the row holds all nine: one lane stores them)
 #pragma unroll
-        for (int k = 1; k < 9; ++k) mine = (p == k) ? nr[k] : mine;
-        nrm[p] = mine;
+        for (int k = 0; k < 9; ++k) nrm[k] = nr[k];
     }
     // sums over the eight lanes of equal parity: halving butterfly (masks 8, 4, 2), 48 -> 6 values per lane
+    const bool up8 = (p & 8) != 0, up4 = (p & 4) != 0, up2 = (p & 2) != 0;   // (once for the 42 steps)
 #pragma unroll
-    for (int i = 0; i < 24; ++i) acc[i] = halve_sum<8>(acc[i], acc[i + 24]);
+    for (int i = 0; i < 24; ++i) acc[i] = halve_sum<8>(acc[i], acc[i + 24], up8);
 #pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = halve_sum<4>(acc[i], acc[i + 12]);
+    for (int i = 0; i < 12; ++i) acc[i] = halve_sum<4>(acc[i], acc[i + 12], up4);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) acc[i] = halve_sum<2>(acc[i], acc[i + 6]);
+    for (int i = 0; i < 6; ++i) acc[i] = halve_sum<2>(acc[i], acc[i + 6], up2);
     // the lane holds local indices base .. base + 5 of its parity's 48 sums; global moment index 48 * parity + local = 16 h + 4 i3 + i2
     const int base = 6 * ((p >> 1) & 1) + 12 * ((p >> 2) & 1) + 24 * ((p >> 3) & 1);
     const double s1 = nr[0], s2 = nr[3], s3 = nr[6];
@@ -240,7 +241,7 @@ __device__ __forceinline__ void rows_min_eigvec(double (&g0)[RowEigDims<n>::N0],
     for (int c = 0; c < N0; ++c) g0[c] = (c < p && valid0) ? g0[c] * myinv0 : 0.0;
     if constexpr (HI) {
 #pragma unroll
-        for (int c = 0; c < n; ++c) g1[c] = (c < 16 + p && valid1) ? g1[c] * myinv1 : 0.0;
+        for (int c = 0; c < n; ++c) g1[c] = ((c < 16 || c < 16 + p) && valid1) ? g1[c] * myinv1 : 0.0;   // (p >= 0: columns below 16 need no compare)
     }
     wave_sync();
     {
@@ -249,7 +250,7 @@ __device__ __forceinline__ void rows_min_eigvec(double (&g0)[RowEigDims<n>::N0],
         for (int c = 0; c < N0; ++c) Lp[(c < p && valid0) ? t0 + c : Z] = g0[c];     // (everything else is 0.0 and lands on the zero slot)
         if constexpr (HI) {
 #pragma unroll
-            for (int c = 0; c < n - 1; ++c) Lp[(c < 16 + p && valid1) ? t1 + c : Z] = g1[c];
+            for (int c = 0; c < n - 1; ++c) Lp[((c < 16 || c < 16 + p) && valid1) ? t1 + c : Z] = g1[c];
         }
     }
     wave_sync();
@@ -362,8 +363,7 @@ __device__ __forceinline__ bool rows_linear_tft_middle(RowLds* w, double* dbg, c
         gram_row27(w->mom, hi ? 16 + p : 0, gb, db);
 #pragma unroll
         for (int c = 0; c < 16; ++c) g0[c] = ga[c];
-#pragma unroll
-        for (int c = 0; c < 27; ++c) gb[c] = hi ? gb[c] : 0.0;
+        // (a position without a hi row factors a copy of row 0 that no other lane ever reads: the solver zeroes it after the factorisation)
         rows_stamp(dbg, 3);
         rows_min_eigvec<27>(g0, gb, da, hi ? db : 0.0, w->ov, EIG_MAXIT, &it1, &r2, false, 0.0, 0.0, &risk, x0, x1);
         ok = ok && eig_converged(r2) && risk == 0.0;
@@ -404,7 +404,8 @@ __device__ __forceinline__ bool rows_linear_tft_middle(RowLds* w, double* dbg, c
         const bool have = p < 15;
         const int r = have ? p : 0;
 #pragma unroll
-        for (int c = 0; c < 15; ++c) { g[c] = (c <= r && have) ? Gp[tri_index(r, c)] : 0.0; diag = (c == r) ? g[c] : diag; }
+        for (int c = 0; c < 15; ++c) g[c] = (c <= r && have) ? Gp[tri_index(r, c)] : 0.0;
+        diag = Gp[tri_index(r, r)];                                          // (read again: one load instead of a 15-way select; a position without a row gets Gp[0], which the solver masks)
         // start from the unconstrained solution projected onto range(E): tp0 = Up' t (tft_kernel.h)
         double tp0 = 0.0;
         if (have) {

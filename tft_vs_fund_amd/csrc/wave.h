@@ -119,12 +119,13 @@ template <> struct Group<16> {
 // On return lane l holds the full 64-lane sum of value index reduce32_index(l).  One halving step: a lane keeps one of two
 // values and adds the other one's copy from lane ^ MASK -- v_permlane32_swap / v_permlane16_swap (swap_sum) for the two widest
 // steps, DPP row / quad operations for the rest; no select on the wide steps, no LDS crossbar anywhere.
+// (up: (lane & MASK) != 0, for the DPP steps.  lane_id() is opaque, so a caller that takes many steps with one MASK works the test out once and
+// passes it: the two-argument form redoes the and + compare at every call)
 template <int MASK>
-__device__ __forceinline__ double halve_sum(double a, double b) {
+__device__ __forceinline__ double halve_sum(double a, double b, const bool up) {
     if constexpr (MASK == 32 || MASK == 16) {
         return swap_sum<MASK>(a, b);
     } else {
-        const bool up = (lane_id() & MASK) != 0;
         const double keep = up ? b : a, send = up ? a : b;
         double got;
         if constexpr (MASK == 8) got = dpp_mov<0x128>(send);                 // row_ror:8 = lane ^ 8 inside a row of 16
@@ -133,6 +134,11 @@ __device__ __forceinline__ double halve_sum(double a, double b) {
         else got = dpp_mov<0xB1>(send);                                      // quad_perm [1,0,3,2]
         return keep + got;
     }
+}
+template <int MASK>
+__device__ __forceinline__ double halve_sum(double a, double b) {
+    if constexpr (MASK == 32 || MASK == 16) return swap_sum<MASK>(a, b);
+    else return halve_sum<MASK>(a, b, (lane_id() & MASK) != 0);
 }
 template <int K>
 __device__ __forceinline__ double wave_reduce_scatter(double (&v)[K]) {

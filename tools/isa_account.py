@@ -19,6 +19,11 @@ Classification is by mnemonic prefix only.
     python tools/isa_account.py                       # k_linear_tft_pose_rows<false, false>
     python tools/isa_account.py --kernel f            # k_linear_f_pose_rows
     python tools/isa_account.py --trips rows_votes@2=7 --out profiles/isa_account_tft.txt
+    python tools/isa_account.py --blocks                # the kernel's basic blocks one by one, in program order
+
+The weighted table multiplies every block of a loop by the loop's trip count, taken or not (the second-candidate blocks of the vote loop
+are never taken at N = 200): it cannot show the executed path.  --blocks lists, per basic block, the VALU count by class, the SALU count,
+whether the block ends in a back edge, and the source lines most of its VALU instructions were inlined from.
 """
 import argparse
 import bisect
@@ -238,6 +243,67 @@ def account(body, findex, depth_frames):
     return result
 
 
+BRANCH = re.compile(r"^s_cbranch_\w+|^s_branch$")
+
+
+def blocks(body):
+    """[(label, Counter of classes + 'salu', ends in a back edge, Counter of innermost source lines of the VALU instructions)] in program order"""
+    out, seen = [], set()
+    label, frames = "entry", []
+    cur = [label, collections.Counter(), False, collections.Counter()]
+    for text in body:
+        m = BLOCK.match(text)
+        if m:
+            if sum(cur[1].values()):
+                out.append(tuple(cur))
+            seen.add(cur[0])
+            label = "BB" + m.group(1) if m.group(1) else text.split("%", 1)[1].split(":")[0]
+            cur = [label, collections.Counter(), False, collections.Counter()]
+            continue
+        if text.lstrip().startswith(".loc"):
+            here = [(f, int(l)) for f, l in FRAME.findall(text.split(";", 1)[1]) if int(l) > 0] if ";" in text else []
+            frames = here or frames
+            continue
+        m = INSTR.match(text)
+        if not m or m.group(1).startswith("."):
+            continue
+        cls = classify(m.group(1), m.group(2))
+        if cls is not None:
+            cur[1][cls] += 1
+            if frames:
+                cur[3]["%s:%d" % (os.path.basename(frames[0][0]), frames[0][1])] += 1
+        elif m.group(1).startswith("s_"):
+            cur[1]["salu"] += 1
+            if BRANCH.match(m.group(1)):
+                target = m.group(2).strip().lstrip(".L")
+                cur[2] = cur[2] or target in seen or target == cur[0]
+    if sum(cur[1].values()):
+        out.append(tuple(cur))
+    return out
+
+
+def blocks_report(lines, kernel, usage):
+    ours = re.compile(r"\d+%s[EI]" % KERNELS[kernel][2])
+    out = ["kernel %s, basic blocks in program order: VALU instructions by class, SALU instructions, back edge, top source lines" % KERNELS[kernel][2]]
+    for k, v in usage:
+        out.append("  %s: %s" % (k, v))
+    for symbol, body in split_functions(lines):
+        if not ours.search(symbol) and re.search(r"\d+k_\w+", symbol):
+            continue
+        out.append("")
+        out.append("function %s" % symbol)
+        out.append("%-12s" % "block" + "".join("%8s" % c for c in CLASSES) + "%8s %6s %6s %5s  %s" % ("VALU", "fp64%", "SALU", "back", "top source lines (VALU instructions)"))
+        total = collections.Counter()
+        for label, c, back, where in blocks(body):
+            n = sum(c[x] for x in CLASSES)
+            total.update(c)
+            out.append("%-12s" % label + "".join("%8d" % c[x] for x in CLASSES) + "%8d %6.1f %6d %5s  %s"
+                       % (n, 100.0 * c["fp64"] / n if n else 0.0, c["salu"], "yes" if back else "", " ".join("%s(%d)" % kv for kv in where.most_common(4))))
+        n = sum(total[x] for x in CLASSES)
+        out.append("%-12s" % "TOTAL" + "".join("%8d" % total[x] for x in CLASSES) + "%8d %6.1f %6d" % (n, 100.0 * total["fp64"] / n if n else 0.0, total["salu"]))
+    return "\n".join(out) + "\n"
+
+
 def main():
     global CSRC
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -247,6 +313,7 @@ def main():
     ap.add_argument("--depth", type=int, default=1, help="inlining depth below the kernel that names a phase (default 1)")
     ap.add_argument("--csrc", default=CSRC, help="kernel sources to compile and to name functions from (default: this tree's; another checkout's for a comparison)")
     ap.add_argument("--asm", help="account an existing assembly file instead of compiling (it must come from the sources under --csrc)")
+    ap.add_argument("--blocks", action="store_true", help="list the basic blocks one by one instead of the two region tables")
     ap.add_argument("--out", help="also write the report to this file")
     args = ap.parse_args()
     CSRC = os.path.abspath(args.csrc)
@@ -264,6 +331,13 @@ def main():
     else:
         with tempfile.TemporaryDirectory() as d:
             lines, usage = build_asm(args.kernel, d)
+    if args.blocks:
+        text = blocks_report(lines, args.kernel, usage)
+        sys.stdout.write(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     findex = FunctionIndex()
     table = collections.OrderedDict()
     assumed = set()
