@@ -91,3 +91,37 @@ def test_mex_gateway_bundle_adjustment_for_four_views(tmp_path):
     blob = np.ascontiguousarray(C2.T).tobytes() + np.ascontiguousarray(CalM[:6].T).tobytes() + np.ascontiguousarray(R0[:6].T).tobytes()
     r = subprocess.run([exe, "bundle_adjustment", "2", str(N)], input=blob, capture_output=True)
     assert r.returncode == 3 and b"tftfund:views" in r.stderr
+
+
+@pytest.mark.gpu
+def test_mex_gateway_passes_three_different_calibrations_through(tmp_path):
+    """mexFunction('linear_tft' / 'linear_f' / 'ressl_tft', Corresp, CalM 9 x 3 with three different blocks -- focal length, principal point, skew and
+    overall scale per view, tests/rig_cases.py) on a rolled rig: MATLAB's column-major CalM reaches the kernels block by block as the ctypes path's does
+    (bit for bit), and that result is the oracle's with the calibration of each view, not the one with K2 and K3 exchanged."""
+    import rig_cases as RC
+    from oracle import tft_oracle as O
+    from tft_vs_fund_amd import api
+    from tft_vs_fund_amd.build import build_library
+    from tft_vs_fund_amd.scenes import calm_colmajor
+    so = build_library()
+    exe = str(tmp_path / "mex_driver")
+    subprocess.run(["gcc", "-std=c99", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + STUB, "-I" + os.path.join(ROOT, "include"), MEX, os.path.join(STUB, "mex_stub.c"),
+                    "-o", exe, "-L" + os.path.dirname(so), "-ltftfund", "-Wl,-rpath," + os.path.dirname(so)], check=True)
+    ctx = api.Context(0)
+    B, N = 5, 40
+    C, CalM, _, _, _ = RC.rig_batch("roll", B, N, 0.5, seed=78, K="shared")
+    assert not np.array_equal(CalM[0:3], CalM[3:6]) and not np.array_equal(CalM[3:6], CalM[6:9])
+    blob = C.tobytes() + calm_colmajor(CalM).tobytes()
+    for mex_name, method in (("linear_tft", "LinearTFTPoseEstimation"), ("ressl_tft", "ResslTFTPoseEstimation"), ("linear_f", "LinearFPoseEstimation")):
+        r = subprocess.run([exe, mex_name, str(B), str(N)], input=blob, capture_output=True, check=True)
+        got = np.frombuffer(r.stdout, dtype=np.float64)
+        assert got.size == B * (12 + 12 + 27 + 1)
+        ref = ctx.pose_batch(method, C, CalM, reconst=True)
+        Rt2 = got[:12 * B].reshape(B, 4, 3).transpose(0, 2, 1); Rt3 = got[12 * B:24 * B].reshape(B, 4, 3).transpose(0, 2, 1)
+        T = got[24 * B:51 * B].reshape(B, 3, 3, 3).transpose(0, 3, 2, 1)
+        assert np.array_equal(Rt2, np.asarray(ref["R_t_2"])) and np.array_equal(Rt3, np.asarray(ref["R_t_3"])) and np.array_equal(T, np.asarray(ref["T"]))
+        for b in range(B):
+            o2, o3 = O.R_t_from_TFT(T[b], CalM, C[b].T.copy())
+            s2, s3 = O.R_t_from_TFT(T[b], RC.swap_views_23(CalM), C[b].T.copy())
+            assert np.abs(Rt2[b] - o2).max() < 1e-9 and np.abs(Rt3[b] - o3).max() < 1e-9 * max(1.0, np.abs(o3).max()), (method, b)
+            assert max(np.abs(Rt2[b] - s2).max(), np.abs(Rt3[b] - s3).max()) > 1e-3, (method, b)

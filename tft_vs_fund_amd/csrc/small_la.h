@@ -544,6 +544,20 @@ __device__ __forceinline__ bool null3(const Mat3& M, double (&x)[3]) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) out[j] = M.m[0][j] * mv[0] + M.m[1][j] * mv[1] + M.m[2][j] * mv[2];
         });
+        if constexpr (GAP_CHECK) {
+            // the same loss on this tier: the certificate above accepts an eigenvector of the formed M'M whose gap is lost (collinear centres, a slice
+            // with singular values 0.70, 5e-6, 0: rotations 7e-10 off a 50-digit evaluation that LAPACK meets at 1e-15 -- tests/test_gpu_rigs.py).
+            // Below the fast tier's limit of 1e-7 tr the one-sided Jacobi on M itself, which never forms the squares, takes over.
+            if (conv) {
+                const double tr = S[0][0] + S[1][1] + S[2][2];
+                double rho = 0.0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) rho += x[i] * (S[i][0] * x[0] + S[i][1] * x[1] + S[i][2] * x[2]);
+                const double c2 = (S[0][0] * S[1][1] - S[0][1] * S[0][1]) + (S[0][0] * S[2][2] - S[0][2] * S[0][2]) + (S[1][1] * S[2][2] - S[1][2] * S[1][2]);
+                const double sm = tr - rho, z = rho + 1e-7 * tr;
+                conv = (z * z - sm * z + (c2 - rho * sm) > 0.0) && (z + z < sm);
+            }
+        }
     } else {
         spd_min_eigvec<3>(S, x, 40, &conv);
         if constexpr (GAP_CHECK) {
