@@ -322,6 +322,9 @@ int tff_bundle_adjust_ragged_host(tff_ctx* ctx, const double* corresp, const int
                                   int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2,
                                   double* Rt3, double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status);
 int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]);
+/* Declared in tftfund_loss.h, which this header includes at its end: robust losses (Huber, Cauchy) for the three-view bundle adjustment.
+ * tff_bundle_adjust_loss_batch_dev / _host and tff_bundle_adjust_loss_ragged_dev / _host take the arguments of the four tff_bundle_adjust_batch_* and
+ * tff_bundle_adjust_ragged_* calls above plus `int32_t loss, double scale, double* weight` at the end.  With TFF_LOSS_NONE they are those calls, bit for bit. */
 
 /* BundleAdjustment (Optimization/BundleAdjustment.m:49-216) as the reference writes it, for M = 2 .. 6 views, in MATLAB's own
  * array layouts so that a gateway passes its arguments through: calm = CalM (3M x 3, column-major; calm_stride 0 = shared, 9M =
@@ -528,4 +531,5 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 #endif
 #include "tftfund_adaptive.h"   /* entry points added after library version 103 */
 #include "tftfund_guided.h"     /* entry points added after library version 104 */
+#include "tftfund_loss.h"       /* entry points added after library version 105 */
 #endif

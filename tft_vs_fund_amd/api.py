@@ -136,9 +136,13 @@ def load_library(path=None):
             "tff_bundle_adjust_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V],
             "tff_bundle_adjust_ragged_class_bounds": [V],
             "tff_optim_f_ragged_bounds": [V],
+            "tff_bundle_adjust_loss_batch_dev": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_bundle_adjust_loss_batch_host": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_bundle_adjust_loss_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_bundle_adjust_loss_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -190,6 +194,10 @@ EXPORTED_SYMBOLS = [
 ADAPTIVE_SYMBOLS = ["tff_robust_pose_scenes_adaptive_dev", "tff_robust_pose_scenes_adaptive_host", "tff_robust_round_plan"]
 # ... and every symbol include/tftfund_guided.h declares: the entry points added after library version 104 (quality-guided sampling)
 GUIDED_SYMBOLS = ["tff_robust_pose_scenes_guided_dev", "tff_robust_pose_scenes_guided_host", "tff_sample_indices_guided_dev"]
+# ... and every symbol include/tftfund_loss.h declares: the entry points added after library version 105 (robust losses in the bundle adjustment)
+LOSS_SYMBOLS = ["tff_bundle_adjust_loss_batch_dev", "tff_bundle_adjust_loss_batch_host", "tff_bundle_adjust_loss_ragged_dev",
+                "tff_bundle_adjust_loss_ragged_host"]
+LOSS_IDS = {"huber": 1, "cauchy": 2}      # include/tftfund_loss.h TFF_LOSS_*; 0 is TFF_LOSS_NONE
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -256,6 +264,22 @@ def adaptive_stop(best, ns, n_sample, qmin, msac=False):
     for _ in range(int(n_sample) - 1):
         q = q * w
     return bool(q >= np.float64(qmin))
+
+
+def _check_loss(loss, scale, what="loss", default_scale=None):
+    """the robust loss of a bundle adjustment: None (and then no scale), or "huber" / "cauchy" with a positive finite scale in pixels
+    -> None or (TFF_LOSS_* id, scale)"""
+    if loss is None:
+        if scale is not None:
+            raise ValueError("a %s scale without a loss" % what)
+        return None
+    if loss not in LOSS_IDS:
+        raise ValueError("%s must be None, 'huber' or 'cauchy', not %r" % (what, loss))
+    if scale is None:
+        scale = default_scale
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (scale > 0 and np.isfinite(scale)):
+        raise ValueError("the scale of the %s must be a positive finite number of pixels, not %r" % (what, scale))
+    return LOSS_IDS[loss], float(scale)
 
 
 def _splitmix64(x):
@@ -784,9 +808,13 @@ class Context:
                                                          self._p(it), self._p(st)), "tff_linear_f_batch_dev")
         return F21.reshape(B, 3, 3).transpose(1, 2), F31.reshape(B, 3, 3).transpose(1, 2), it, st
 
-    def bundle_adjust(self, calm, R_t_2, R_t_3, corresp, reconst0=None):
+    def bundle_adjust(self, calm, R_t_2, R_t_3, corresp, reconst0=None, loss=None, scale=None):
         """BundleAdjustment for B triplets: calm (9,3) or (B,9,3); R_t_2, R_t_3 (B,3,4); corresp (B,N,6); reconst0 (B,3,N) or None.
-        -> dict(R_t_2, R_t_3 (B,3,4), Reconst (B,3,N), iter, repr_err, status)."""
+        -> dict(R_t_2, R_t_3 (B,3,4), Reconst (B,3,N), iter, repr_err, status).
+        loss = "huber" or "cauchy" with scale = c in pixels (tff_bundle_adjust_loss_batch_dev, include/tftfund_loss.h): the adjustment minimises
+        sum rho(|pixel residual|^2) by reweighted Levenberg-Marquardt, repr_err is the square root of that sum, and weight (B,N), rho' at the final
+        parameters, joins the dict.  Without a loss nothing changes."""
+        robust = _check_loss(loss, scale)
         self._begin()
         corresp = self._t(corresp); B, N, _ = corresp.shape
         dev = corresp.device
@@ -801,20 +829,28 @@ class Context:
         rec = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
         it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it)
         err = torch.empty(B, dtype=torch.float64, device=dev)
-        _check(self.lib, self.lib.tff_bundle_adjust_batch_dev(self.handle, self._p(calm_cm), stride, self._p(r2), self._p(r3), self._p(corresp), B, N,
-                                                              self._p(x0), self._p(o2), self._p(o3), self._p(rec), self._p(it), self._p(err), self._p(st)),
-               "tff_bundle_adjust_batch_dev")
-        return dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec.transpose(1, 2),
-                    iter=it, repr_err=err, status=st)
+        a = (self.handle, self._p(calm_cm), stride, self._p(r2), self._p(r3), self._p(corresp), B, N, self._p(x0), self._p(o2), self._p(o3), self._p(rec),
+             self._p(it), self._p(err), self._p(st))
+        out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec.transpose(1, 2),
+                   iter=it, repr_err=err, status=st)
+        if robust is None:
+            _check(self.lib, self.lib.tff_bundle_adjust_batch_dev(*a), "tff_bundle_adjust_batch_dev")
+        else:
+            out["weight"] = torch.empty((B, N), dtype=torch.float64, device=dev)
+            _check(self.lib, self.lib.tff_bundle_adjust_loss_batch_dev(*a, robust[0], robust[1], self._p(out["weight"])), "tff_bundle_adjust_loss_batch_dev")
+        return out
 
-    def bundle_adjust_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, mask=None, reconst0=None, reconst=True):
+    def bundle_adjust_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, mask=None, reconst0=None, reconst=True, loss=None, scale=None):
         """BundleAdjustment for B items with different correspondence counts in one call (tff_bundle_adjust_ragged_*): corresp (Ntot, 6) packed,
         offsets (B + 1,) int64 with item b = corresp[offsets[b]:offsets[b + 1]] (see pack_ragged), mask None or (Ntot,) uint8 / bool (non-zero = use the
         correspondence: the `mask` of robust_pose_scenes), calm (9, 3) or (B, 9, 3), R_t_2, R_t_3 (B, 3, 4), reconst0 None or (Ntot, 3) (read where
         selected).  Item b gets bit for bit what bundle_adjust returns for its selected correspondences alone.  CUDA tensors in (offsets on the device)
         -> CUDA tensors out, no synchronisation; numpy in -> numpy out through the _host form (malformed offsets raise).
         Returns dict(R_t_2, R_t_3 (B,3,4), Reconst (Ntot,3) or None -- NaN where not selected --, iter, repr_err, used, status (B,)); per item
-        ST_BAD_OFFSETS / ST_TOO_FEW (nothing selected) / ST_TOO_LARGE (more than BA_MAX_N selected) with NaN poses."""
+        ST_BAD_OFFSETS / ST_TOO_FEW (nothing selected) / ST_TOO_LARGE (more than BA_MAX_N selected) with NaN poses.
+        loss, scale: as bundle_adjust (tff_bundle_adjust_loss_ragged_*); weight (Ntot,), packed like corresp, joins the dict: NaN where the mask
+        deselects and over an item that failed.  Item b still equals bundle_adjust with the same loss on its selection, bit for bit."""
+        robust = _check_loss(loss, scale)
         host = isinstance(corresp, np.ndarray)
         if host:
             offsets = np.asarray(offsets)
@@ -854,11 +890,16 @@ class Context:
             rec = np.full((ntot, 3), np.nan) if reconst else None
             it = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32); used = np.zeros(B, dtype=np.int32); err = np.empty(B)
             ptr = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None else None
-            _check(self.lib, self.lib.tff_bundle_adjust_ragged_host(self.handle, ptr(corresp), ptr(offsets), ptr(mk), ptr(calm_cm), stride, ptr(r2), ptr(r3),
-                                                                    ptr(x0), B, ptr(o2), ptr(o3), ptr(rec), ptr(it), ptr(err), ptr(used), ptr(st)),
-                   "tff_bundle_adjust_ragged_host")
-            return dict(R_t_2=o2.reshape(B, 4, 3).transpose(0, 2, 1), R_t_3=o3.reshape(B, 4, 3).transpose(0, 2, 1), Reconst=rec, iter=it, repr_err=err,
-                        used=used, status=st)
+            a = (self.handle, ptr(corresp), ptr(offsets), ptr(mk), ptr(calm_cm), stride, ptr(r2), ptr(r3), ptr(x0), B, ptr(o2), ptr(o3), ptr(rec), ptr(it),
+                 ptr(err), ptr(used), ptr(st))
+            out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(0, 2, 1), R_t_3=o3.reshape(B, 4, 3).transpose(0, 2, 1), Reconst=rec, iter=it, repr_err=err,
+                       used=used, status=st)
+            if robust is None:
+                _check(self.lib, self.lib.tff_bundle_adjust_ragged_host(*a), "tff_bundle_adjust_ragged_host")
+            else:
+                out["weight"] = np.full(ntot, np.nan)
+                _check(self.lib, self.lib.tff_bundle_adjust_loss_ragged_host(*a, robust[0], robust[1], ptr(out["weight"])), "tff_bundle_adjust_loss_ragged_host")
+            return out
         dev = corresp.device
         calm_cm, stride = self._calm_scenes(calm, B, dev)
         on_dev = lambda a, dt: (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(device=dev, dtype=dt)
@@ -870,26 +911,42 @@ class Context:
         it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it); used = torch.zeros_like(it)
         err = torch.empty(B, dtype=torch.float64, device=dev)
         self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _check(self.lib, self.lib.tff_bundle_adjust_ragged_dev(self.handle, self._p(corresp), self._p(offsets), ntot, self._p(mk), self._p(calm_cm), stride,
-                                                               self._p(r2), self._p(r3), self._p(x0), B, self._p(o2), self._p(o3), self._p(rec), self._p(it),
-                                                               self._p(err), self._p(used), self._p(st)), "tff_bundle_adjust_ragged_dev")
-        return dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec, iter=it, repr_err=err, used=used,
-                    status=st)
+        a = (self.handle, self._p(corresp), self._p(offsets), ntot, self._p(mk), self._p(calm_cm), stride, self._p(r2), self._p(r3), self._p(x0), B,
+             self._p(o2), self._p(o3), self._p(rec), self._p(it), self._p(err), self._p(used), self._p(st))
+        out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec, iter=it, repr_err=err, used=used,
+                   status=st)
+        if robust is None:
+            _check(self.lib, self.lib.tff_bundle_adjust_ragged_dev(*a), "tff_bundle_adjust_ragged_dev")
+        else:
+            out["weight"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
+            _check(self.lib, self.lib.tff_bundle_adjust_loss_ragged_dev(*a, robust[0], robust[1], self._p(out["weight"])), "tff_bundle_adjust_loss_ragged_dev")
+        return out
 
     @staticmethod
     def _refined(out, r):
         """the refine step of robust_pose_scenes: the outputs of its one pose_batch_ragged call under their names"""
         out.update(R_t_2_refined=r["R_t_2"], R_t_3_refined=r["R_t_3"], T_refined=r["T"], iter_refined=r["iter"], status_refined=r["status"])
 
-    def _polish(self, out, calm, scenes, offsets, single):
-        """the polish of robust_pose / robust_pose_scenes: ONE bundle_adjust_ragged call on the result's poses and mask"""
+    @staticmethod
+    def _check_polish(polish_loss, polish_scale, polish_all, threshold):
+        """the polish arguments of the robust calls -> (loss, scale, all matches)"""
+        robust = _check_loss(polish_loss, polish_scale, "polish_loss", threshold)
+        if polish_all and robust is None:
+            raise ValueError("polish_all=True adjusts over all matches of a scene, wrong ones included: it needs a polish_loss")
+        return (polish_loss, None if robust is None else robust[1], bool(polish_all))
+
+    def _polish(self, out, calm, scenes, offsets, single, how=(None, None, False)):
+        """the polish of robust_pose / robust_pose_scenes: ONE bundle_adjust_ragged call on the result's poses and mask (how: _check_polish -- with a
+        loss, and then over the mask or over all matches)"""
         r2, r3 = out["R_t_2"], out["R_t_3"]
         if single:
             r2, r3 = r2[None], r3[None]
-        ba = self.bundle_adjust_ragged(calm, r2, r3, scenes, offsets, mask=out["mask"], reconst=False)
+        ba = self.bundle_adjust_ragged(calm, r2, r3, scenes, offsets, mask=None if how[2] else out["mask"], reconst=False, loss=how[0], scale=how[1])
         pick = (lambda a: a[0]) if single else (lambda a: a)
         out.update(R_t_2_polished=pick(ba["R_t_2"]), R_t_3_polished=pick(ba["R_t_3"]), iter_polished=pick(ba["iter"]),
                    repr_err_polished=pick(ba["repr_err"]), status_polished=pick(ba["status"]))
+        if how[0] is not None:
+            out["weight_polished"] = ba["weight"]                            # packed like mask
         return out
 
     def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None):
@@ -996,7 +1053,7 @@ class Context:
         return (mask, cnt) if with_counts else mask
 
     def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False,
-                    confidence=None, first_round=256, order=None, quality=None, growth=200000):
+                    confidence=None, first_round=256, order=None, quality=None, growth=200000, polish_loss=None, polish_scale=None, polish_all=False):
         """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
         best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
         Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
@@ -1009,7 +1066,9 @@ class Context:
         confidence = c in (0, 1): the early stop of robust_pose_scenes for this one scene (the S = 1 call with the offsets [0, Ns]): n_hyp is the cap,
         first_round the first round's length, and n_hyp_used joins the dict; the result is that of this call with n_hyp = n_hyp_used.
         order= (Ns,) int32, the matches best first, or quality= (Ns,) float, higher is better, with growth: the guided sampler of robust_pose_scenes for
-        this one scene (the S = 1 call with the offsets [0, Ns]); n_hyp_used joins the dict only with a confidence.  Without them nothing changes."""
+        this one scene (the S = 1 call with the offsets [0, Ns]); n_hyp_used joins the dict only with a confidence.  Without them nothing changes.
+        polish_loss, polish_scale, polish_all: as robust_pose_scenes; weight_polished (Ns,) joins the dict."""
+        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold)
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
@@ -1077,7 +1136,7 @@ class Context:
             out.update(R_t_2_refined=r["R_t_2"][0], R_t_3_refined=r["R_t_3"][0], T_refined=r["T"][0], iter_refined=r["iter"][0],
                        status_refined=r["status"][0])
         if polish:
-            self._polish(out, calm, sc, offsets, True)
+            self._polish(out, calm, sc, offsets, True, how)
             if host:
                 out["iter_polished"] = int(out["iter_polished"]); out["status_polished"] = int(out["status_polished"])
                 out["repr_err_polished"] = float(out["repr_err_polished"])
@@ -1129,7 +1188,8 @@ class Context:
         return out
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
-                           polish=False, refine=None, confidence=None, first_round=256, order=None, quality=None, growth=200000):
+                           polish=False, refine=None, confidence=None, first_round=256, order=None, quality=None, growth=200000, polish_loss=None,
+                           polish_scale=None, polish_all=False):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
@@ -1152,7 +1212,13 @@ class Context:
         (Ntot,) float, higher is better and NaN last, is turned into it by stable sorts (order_from_quality; torch on the device path, no
         synchronisation).  The early hypotheses draw from the best-ranked matches, and after `growth` draws per scene the sampling is the uniform one
         (sample_indices_guided_reference is the definition).  Scene s still equals its own one-scene call with seed + s, and confidence, refine, polish
-        and set_score("msac") compose as without a ranking; the stop rule is the existing one.  Without either argument growth is ignored."""
+        and set_score("msac") compose as without a ranking; the stop rule is the existing one.  Without either argument growth is ignored.
+        polish_loss = "huber" or "cauchy": the polish minimises that robust loss (bundle_adjust_ragged(..., loss=, scale=)) with polish_scale pixels,
+        by default `threshold`; weight_polished (Ntot,), packed like mask, joins the dict.  polish_all=True passes no mask: the polish runs over all
+        matches of every scene and the loss alone keeps the wrong ones down (refused without a loss).  A scene without a pose then enters the adjustment
+        with its NaN poses and leaves it with ST_NONFINITE, NaN poses and NaN weights (under the mask: ST_TOO_FEW, as before).  The three are checked before anything else and
+        otherwise ignored without polish=True."""
+        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold)
         adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
         guided = self._check_guided(scenes, order, quality, growth)
         if refine is not None and refine not in RAGGED_METHODS:
@@ -1186,7 +1252,7 @@ class Context:
                 inl = np.ascontiguousarray(sc[keep])
                 cum = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
                 self._refined(out, self.pose_batch_ragged(refine, inl, cum[offsets], calm, reconst=False))
-            return self._polish(out, calm, sc, offsets, False) if polish else out
+            return self._polish(out, calm, sc, offsets, False, how) if polish else out
         if not (isinstance(scenes, torch.Tensor) and scenes.is_cuda and scenes.dtype == torch.float64 and scenes.is_contiguous() and scenes.dim() == 2
                 and scenes.shape[1] == 6):
             raise ValueError("scenes must be a contiguous float64 CUDA tensor of shape (Ntot, 6)")
@@ -1224,7 +1290,7 @@ class Context:
             packed = scenes[torch.argsort(1 - keep, stable=True)]
             cum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(keep, 0)])
             self._refined(out, self.pose_batch_ragged(refine, packed, cum[offsets.clamp(0, ntot)], calm, reconst=False, n_max=int(ns_max)))
-        return self._polish(out, calm, scenes, offsets, False) if polish else out
+        return self._polish(out, calm, scenes, offsets, False, how) if polish else out
 
     def inlier_count_scenes(self, scenes, offsets, calm, R_t_2, R_t_3, threshold=1.0):
         """Inlier counts of S * per_scene pose hypotheses against S packed scenes (tff_inlier_count_scenes_dev): R_t_2, R_t_3 (S * per_scene, 3, 4),

@@ -50,6 +50,60 @@ struct BaArgs {
     const int* items = nullptr; const int* count = nullptr; const int* item_n = nullptr; const long* item_off = nullptr;
 };
 
+// Robust losses (tff_bundle_adjust_loss_*; tests/ba_loss_oracle.py is the definition).  With a loss the adjustment minimises F = sum_i rho(|e_i|^2) over
+// the PIXEL residual e_{i,v} = r_{i,v} / s_v (s_v the scale of view v's Normalize2Ddata matrix) by iteratively reweighted Levenberg-Marquardt: at the
+// current parameters w_i = rho'(|e_i|^2), and the residual rows of correspondence i in view v with the same rows of both Jacobians are multiplied by
+// sqrt(w_i) / s_v before anything is accumulated (no second-order correction); the costs that steer acceptance are sum rho, without frozen weights.
+// The loss is a compile-time parameter: everything below that it adds sits under `if constexpr`, and instance 0 is the plain kernel, instruction for
+// instruction.  The scale c and the three 1 / s_v are wave-uniform values in registers: the loss costs no LDS.
+constexpr int BA_LOSS_NONE = 0, BA_LOSS_HUBER = 1, BA_LOSS_CAUCHY = 2;
+struct BaLossArgs : BaArgs {
+    double scale = 0.0;                              // c, in pixels
+    double* weight = nullptr;                        // w_i at the final parameters, indexed like corresp (B x N, or packed); NaN for an item that failed; may be null
+};
+template <int LOSS> struct BaLoss { double is[3], c, c2, ic2; };   // 1 / s_v, c, c^2, 1 / c^2
+template <> struct BaLoss<BA_LOSS_NONE> {};
+
+// |e|^2 of one correspondence from its normalised residual
+template <int LOSS>
+__device__ __forceinline__ double ba_e2(const BaLoss<LOSS>& ls, const double (&r)[6]) {
+    double s = 0.0;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) { const double ex = r[2 * v] * ls.is[v], ey = r[2 * v + 1] * ls.is[v]; s += ex * ex + ey * ey; }
+    return s;
+}
+template <int LOSS>
+__device__ __forceinline__ double ba_rho(const BaLoss<LOSS>& ls, const double s) {
+    if constexpr (LOSS == BA_LOSS_HUBER) return (s <= ls.c2) ? s : 2.0 * ls.c * sqrt(s) - ls.c2;
+    else return ls.c2 * log1p(s * ls.ic2);
+}
+template <int LOSS>
+__device__ __forceinline__ double ba_rho1(const BaLoss<LOSS>& ls, const double s) {
+    if constexpr (LOSS == BA_LOSS_HUBER) return (s <= ls.c2) ? 1.0 : ls.c / sqrt(s);
+    else return 1.0 / (1.0 + s * ls.ic2);
+}
+// the weight of one correspondence from the residual its sweep already has, and the rows of r, Jp, Jc times sqrt(w) / s_v
+template <int LOSS>
+__device__ __forceinline__ void ba_weigh(const BaLoss<LOSS>& ls, double (&r)[6], double (&Jp)[6][3], double (&Jc)[2][2][6]) {
+    if constexpr (LOSS != BA_LOSS_NONE) {
+        const double sw = sqrt(ba_rho1<LOSS>(ls, ba_e2<LOSS>(ls, r)));
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const double f = sw * ls.is[v];
+#pragma unroll
+            for (int row = 2 * v; row < 2 * v + 2; ++row) {
+                r[row] *= f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) Jp[row][k] *= f;
+                if (v > 0) {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) Jc[v - 1][row - 2 * v][k] *= f;
+                }
+            }
+        }
+    }
+}
+
 // lane 0: rotation products of one camera from its three angles
 __device__ inline void ba_prepare_camera(const double* K, const double* ang, const double* t, double* KR, double* Kt, double (*KdR)[9]) {
     const double cx = cos(ang[0]), sx = sin(ang[0]), cy = cos(ang[1]), sy = sin(ang[1]), cz = cos(ang[2]), sz = sin(ang[2]);
@@ -133,8 +187,8 @@ __host__ __device__ constexpr int ba_cam_of(int p) { return (p / 3) & 1; }
 __host__ __device__ constexpr int ba_col_of(int p) { return (p % 3) + 3 * (p / 6); }
 
 // one accumulation sweep: entries [30 SW, 30 SW + 30) of (lower triangle of the 12 x 12 Schur matrix, then the 12 right-hand sides)
-template <int SW>
-__device__ inline void ba_sweep(BaLds* L, const double* pts, const double* nrm, const double* Xs, int N, double lambda) {
+template <int SW, int LOSS>
+__device__ inline void ba_sweep(BaLds* L, const double* pts, const double* nrm, const double* Xs, int N, double lambda, const BaLoss<LOSS> ls) {
     const int lane = lane_id();
     double acc[32];
 #pragma unroll
@@ -145,6 +199,7 @@ __device__ inline void ba_sweep(BaLds* L, const double* pts, const double* nrm, 
         const double X[3] = {Xs[3 * i], Xs[3 * i + 1], Xs[3 * i + 2]};
         double r[6], Jp[6][3], Jc[2][2][6], Vi[6];
         ba_point<true>(L, &L->cur, x, X, r, Jp, Jc);
+        ba_weigh<LOSS>(ls, r, Jp, Jc);
         ba_vinv(Jp, lambda, Vi);
         // P = I - Jp inv(V) Jp' restricted to the rows of views 2, 3 (rows 2..5), and s = P r on those rows (r uses all six rows)
         double G[6][3];                                                      // Jp inv(V)
@@ -188,21 +243,28 @@ __device__ inline void ba_sweep(BaLds* L, const double* pts, const double* nrm, 
     if ((lane & 1) == 0 && idx < 30) L->H[30 * SW + idx] = tot;
 }
 
-// sum of squared residuals of parameter set `cam` with points Xs
-__device__ inline double ba_cost(const BaLds* L, const BaCams* cam, const double* pts, const double* nrm, const double* Xs, int N) {
+// sum of squared residuals of parameter set `cam` with points Xs (with a loss: sum of rho(|e|^2))
+template <int LOSS>
+__device__ inline double ba_cost(const BaLds* L, const BaCams* cam, const double* pts, const double* nrm, const double* Xs, int N, const BaLoss<LOSS> ls) {
     double S = 0.0;
     for (int i = lane_id(); i < N; i += WAVE) {
         const Pt6 x = premap(load_pt(pts, i), nrm);
         const double X[3] = {Xs[3 * i], Xs[3 * i + 1], Xs[3 * i + 2]};
         double r[6], Jp[6][3], Jc[2][2][6];
         ba_point<false>(L, cam, x, X, r, Jp, Jc);
+        if constexpr (LOSS == BA_LOSS_NONE) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) S += r[k] * r[k];
+            for (int k = 0; k < 6; ++k) S += r[k] * r[k];
+        } else {
+            S += ba_rho<LOSS>(ls, ba_e2<LOSS>(ls, r));
+        }
     }
     return wave_sum(S);
 }
 
-__global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
+// ARGS is BaArgs for LOSS = 0 and BaLossArgs otherwise; the names the launchers use follow the kernel.
+template <int LOSS, class ARGS>
+__global__ void __launch_bounds__(64, 1) k_bundle_adjust_t(const ARGS a) {
     TFF_DYNAMIC_LDS(double, smem);
     PoseLds* w = reinterpret_cast<PoseLds*>(smem);
     constexpr int base = (POSE_LDS_DOUBLES + 1) & ~1;
@@ -227,6 +289,12 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
         if (lane < 27) w->calm[lane] = a.calm[b * a.calm_stride + lane];
         wave_sync();
         normalise3(pts, N, w->nrm);                                          // :52-54
+        BaLoss<LOSS> ls;
+        if constexpr (LOSS != BA_LOSS_NONE) {
+#pragma unroll
+            for (int v = 0; v < 3; ++v) ls.is[v] = wave_uniform(1.0 / w->nrm[3 * v]);
+            ls.c = a.scale; ls.c2 = a.scale * a.scale; ls.ic2 = 1.0 / ls.c2;
+        }
         if (lane < 27) {                                                     // CalM(3j-2:3j,:) = Normal * CalM(...)   (:55)
             const int v = lane / 9, r = (lane % 9) / 3, c = lane % 3;
             const Mat3 Nm = normal_matrix(w->nrm, v);
@@ -261,13 +329,13 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
         ba_prepare(L, &L->cur);
         // ---- Levenberg-Marquardt (oracle/ba_oracle.py: levenberg_marquardt) ----
         double lambda = BA_INIT_DAMPING;
-        double S = ba_cost(L, &L->cur, pts, w->nrm, Xc, N);
+        double S = ba_cost<LOSS>(L, &L->cur, pts, w->nrm, Xc, N, ls);
         int it = 0, status = ST_OK;
 #pragma unroll 1
         while (it < BA_MAX_ITER) {
-            ba_sweep<0>(L, pts, w->nrm, Xc, N, lambda);
-            ba_sweep<1>(L, pts, w->nrm, Xc, N, lambda);
-            ba_sweep<2>(L, pts, w->nrm, Xc, N, lambda);
+            ba_sweep<0, LOSS>(L, pts, w->nrm, Xc, N, lambda, ls);
+            ba_sweep<1, LOSS>(L, pts, w->nrm, Xc, N, lambda, ls);
+            ba_sweep<2, LOSS>(L, pts, w->nrm, Xc, N, lambda, ls);
             wave_sync();
             for (int e = lane; e < 12 * 13; e += WAVE) {                     // (sum Jc' P Jc + lambda I) dc = -sum Jc' P r
                 const int r = e / 13, c = e % 13;
@@ -277,21 +345,28 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
                 L->M[e] = v;
             }
             wave_sync();
-            const bool ok = wave_solve_gj<12>(L->M, L->dc);
+            // (With a loss the system is in pixels: its entries are 1 / s_v^2, some 1e4 .. 1e5, times the plain ones, the damping is not, and the pivot
+            // of the scale gauge is the damping alone.  The plain floor of 1e-10 of the largest entry would stop a run after its second success; the
+            // restatement solves without a floor, so the loss instances ask for a positive pivot only.)
+            const bool ok = (LOSS == BA_LOSS_NONE) ? wave_solve_gj<12>(L->M, L->dc) : wave_solve_gj<12>(L->M, L->dc, 0.0);
             if (!ok) { status = ST_NONFINITE; break; }
-            if (lane < 12) L->trial.c[lane] = L->cur.c[lane] + L->dc[lane];
-            wave_sync();
-            ba_prepare(L, &L->trial);
+            if constexpr (LOSS == BA_LOSS_NONE) {                            // (with a loss: after the step has lost its gauge component, below)
+                if (lane < 12) L->trial.c[lane] = L->cur.c[lane] + L->dc[lane];
+                wave_sync();
+                ba_prepare(L, &L->trial);
+            }
             double dc[12];
 #pragma unroll
             for (int k = 0; k < 12; ++k) dc[k] = wave_uniform(L->dc[k]);
             // dX_i = -inv(V_i) Jp_i' (r_i + Jc_i dc); trial cost; norms for the step test
             double St = 0.0, step2 = 0.0, x2 = 0.0;
+            [[maybe_unused]] double vs = 0.0;                                // with a loss: v . step over the points, v = (0, t2, t3, X) the scale gauge
             for (int i = lane; i < N; i += WAVE) {
                 const Pt6 x = premap(load_pt(pts, i), w->nrm);
                 const double X[3] = {Xc[3 * i], Xc[3 * i + 1], Xc[3 * i + 2]};
                 double r[6], Jp[6][3], Jc[2][2][6], Vi[6];
                 ba_point<true>(L, &L->cur, x, X, r, Jp, Jc);
+                ba_weigh<LOSS>(ls, r, Jp, Jc);
                 ba_vinv(Jp, lambda, Vi);
 #pragma unroll
                 for (int cj = 0; cj < 2; ++cj)
@@ -309,12 +384,54 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
                 double Xn[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { Xn[k] = X[k] - dX[k]; Xt[3 * i + k] = Xn[k]; step2 += dX[k] * dX[k]; x2 += X[k] * X[k]; }
-                double rt[6], Jp2[6][3], Jc2[2][2][6];
-                ba_point<false>(L, &L->trial, x, Xn, rt, Jp2, Jc2);
+                if constexpr (LOSS == BA_LOSS_NONE) {
+                    double rt[6], Jp2[6][3], Jc2[2][2][6];
+                    ba_point<false>(L, &L->trial, x, Xn, rt, Jp2, Jc2);
 #pragma unroll
-                for (int k = 0; k < 6; ++k) St += rt[k] * rt[k];
+                    for (int k = 0; k < 6; ++k) St += rt[k] * rt[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) vs -= X[k] * dX[k];
+                }
             }
-            St = wave_sum(St); step2 = wave_sum(step2); x2 = wave_sum(x2);
+            if constexpr (LOSS == BA_LOSS_NONE) {
+                St = wave_sum(St); step2 = wave_sum(step2); x2 = wave_sum(x2);
+            } else {
+                // The cost does not change along v = (0, t2, t3, X), the common scale of the translations and the points: J v = 0, so v . gradient = 0 and
+                // the step of the loop has NO component along v.  In pixels nothing but the damping -- 1e-11 and less of the matrix -- stands in that
+                // direction, and rounding puts a component of any size there (the scale of the solution wandered by 1e-4 between two orders of
+                // summation, which left 1e-9 in the normalised poses).  The component is therefore set to its exact value, zero: step -= v (v . step) / (v . v).
+                vs = wave_sum(vs); x2 = wave_sum(x2);
+                double vv = x2;
+#pragma unroll
+                for (int k = 6; k < 12; ++k) { const double tk = wave_uniform(L->cur.c[k]); vs += tk * dc[k]; vv += tk * tk; }
+                const double beta = vs / vv;
+                if (lane < 12) {
+                    const double d = L->dc[lane] - ((lane >= 6) ? beta * L->cur.c[lane] : 0.0);
+                    L->dc[lane] = d;
+                    L->trial.c[lane] = L->cur.c[lane] + d;
+                }
+                wave_sync();
+                ba_prepare(L, &L->trial);
+#pragma unroll
+                for (int k = 0; k < 12; ++k) dc[k] = wave_uniform(L->dc[k]);
+                step2 = 0.0;
+                for (int i = lane; i < N; i += WAVE) {                       // the trial points without the gauge component, and the trial cost
+                    const Pt6 x = premap(load_pt(pts, i), w->nrm);
+                    double Xn[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double Xk = Xc[3 * i + k];
+                        Xn[k] = Xt[3 * i + k] - beta * Xk;
+                        Xt[3 * i + k] = Xn[k];
+                        step2 += (Xn[k] - Xk) * (Xn[k] - Xk);
+                    }
+                    double rt[6], Jp2[6][3], Jc2[2][2][6];
+                    ba_point<false>(L, &L->trial, x, Xn, rt, Jp2, Jc2);
+                    St += ba_rho<LOSS>(ls, ba_e2<LOSS>(ls, rt));
+                }
+                St = wave_sum(St); step2 = wave_sum(step2);
+            }
 #pragma unroll
             for (int k = 0; k < 12; ++k) { step2 += dc[k] * dc[k]; const double ck = wave_uniform(L->cur.c[k]); x2 += ck * ck; }
             const bool small_step = sqrt(step2) < BA_TOL_X * (1.4901161193847656e-08 + sqrt(x2));
@@ -353,8 +470,22 @@ __global__ void __launch_bounds__(64, 1) k_bundle_adjust(const BaArgs a) {
             if (a.repr_err) a.repr_err[b] = sqrt(S);                         // norm(func(variables))   (:105)
             if (a.status) a.status[b] = status;
         }
+        if constexpr (LOSS != BA_LOSS_NONE) {                                // w_i at the final parameters
+            if (a.weight) {
+                for (int i = lane; i < N; i += WAVE) {
+                    const Pt6 x = premap(load_pt(pts, i), w->nrm);
+                    const double X[3] = {Xc[3 * i], Xc[3 * i + 1], Xc[3 * i + 2]};
+                    double r[6], Jp[6][3], Jc[2][2][6];
+                    ba_point<false>(L, &L->cur, x, X, r, Jp, Jc);
+                    a.weight[first + i] = (status == ST_OK) ? ba_rho1<LOSS>(ls, ba_e2<LOSS>(ls, r)) : __longlong_as_double(0x7ff8000000000000LL);
+                }
+            }
+        }
     }
 }
+
+inline constexpr auto k_bundle_adjust = &k_bundle_adjust_t<BA_LOSS_NONE, BaArgs>;           // the plain kernel
+template <int LOSS> inline constexpr auto k_bundle_adjust_loss = &k_bundle_adjust_t<LOSS, BaLossArgs>;
 
 constexpr size_t ba_lds_bytes(int N) {
     return (size_t)(((POSE_LDS_DOUBLES + 1) & ~1) + ((BA_LDS_DOUBLES + 1) & ~1) + 6 * (size_t)N) * sizeof(double);

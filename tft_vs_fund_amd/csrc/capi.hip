@@ -22,6 +22,7 @@
 #include "robust_guided_kernel.h"
 #include "robust_layout.h"
 #include "ba_ragged_kernel.h"
+#include "ba_loss_kernel.h"
 
 namespace {
 
@@ -79,6 +80,7 @@ struct tff_ctx {
     DevBuf ragged, ragged_off;             // ragged batches: the plan (buckets, slot list), the offsets of a _host call
     DevBuf robust_hyp, robust_counts, robust_cand;   // the robust estimators, one scene or many: one chunk of hypotheses, the counts of all of them, the candidates' state (launch_robust_scenes)
     DevBuf guided_ends, guided_order;      // guided sampling: the pool tables (4 n_total bytes), the ranking of a _host call (4 n_total bytes)
+    DevBuf ba_weight;                      // tff_bundle_adjust_loss_*_host: the staged weights
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
@@ -1061,7 +1063,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 105; }
+int tff_version(void) { return 106; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1087,7 +1089,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight})
         b->release();
     delete c;
 }
@@ -1500,9 +1502,29 @@ int tff_linear_tft_batch_dev(tff_ctx* c, const double* corresp, int64_t B, int32
 namespace {
 
 // ---- bundle adjustment ------------------------------------------------------------------------------------------------------------------------
-int launch_bundle_adjust(tff_ctx* c, const tff::BaArgs& a) {
+static_assert(TFF_LOSS_NONE == tff::BA_LOSS_NONE && TFF_LOSS_HUBER == tff::BA_LOSS_HUBER && TFF_LOSS_CAUCHY == tff::BA_LOSS_CAUCHY, "loss codes");
+int check_loss(int32_t loss, double scale) {
+    if (loss != TFF_LOSS_NONE && loss != TFF_LOSS_HUBER && loss != TFF_LOSS_CAUCHY) return fail(TFF_E_INVALID, "loss must be TFF_LOSS_NONE, TFF_LOSS_HUBER or TFF_LOSS_CAUCHY");
+    if (loss != TFF_LOSS_NONE && !(scale > 0.0 && std::isfinite(scale))) return fail(TFF_E_INVALID, "the scale of a loss must be a positive finite number");
+    return 0;
+}
+// the instance of k_bundle_adjust_loss for a loss other than TFF_LOSS_NONE (that one is k_bundle_adjust itself)
+int launch_ba_loss(tff_ctx* c, int32_t loss, unsigned grid, size_t lds, const tff::BaLossArgs& a) {
+    return loss == TFF_LOSS_HUBER ? launch(c, tff::k_bundle_adjust_loss<tff::BA_LOSS_HUBER>, grid, 64, lds, a)
+                                  : launch(c, tff::k_bundle_adjust_loss<tff::BA_LOSS_CAUCHY>, grid, 64, lds, a);
+}
+int launch_bundle_adjust(tff_ctx* c, const tff::BaArgs& a, int32_t loss = TFF_LOSS_NONE, double scale = 0.0, double* weight = nullptr) {
     if (a.N < 1) return fail(TFF_E_INVALID, "bundle adjustment needs at least one correspondence");
-    return launch(c, tff::k_bundle_adjust, tff::pose_grid(a.B), 64, tff::ba_lds_bytes(a.N), a);
+    if (loss == TFF_LOSS_NONE) {
+        TFF_TRY(launch(c, tff::k_bundle_adjust, tff::pose_grid(a.B), 64, tff::ba_lds_bytes(a.N), a));
+        if (!weight) return 0;
+        const long blocks = (a.B * (long)a.N + 255) / 256;
+        return launch(c, tff::k_ba_weight_ones, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, tff::BaOnesArgs{weight, a.status, a.B, a.N});
+    }
+    tff::BaLossArgs la;
+    static_cast<tff::BaArgs&>(la) = a;
+    la.scale = scale; la.weight = weight;
+    return launch_ba_loss(c, loss, tff::pose_grid(a.B), tff::ba_lds_bytes(a.N), la);
 }
 // ---- ragged, masked bundle adjustment (tff_bundle_adjust_ragged_*; the chain is described in ba_ragged_kernel.h) -------------------------------
 static_assert(TFF_BA_MAX_N == tff::BA_CLASS_BOUND_2 && tff::ba_lds_bytes(TFF_BA_MAX_N) <= LDS_LIMIT && tff::ba_lds_bytes(TFF_BA_MAX_N + 1) > LDS_LIMIT,
@@ -1517,6 +1539,7 @@ struct BaRaggedCall {                      // device pointers
     const double* corresp; const int64_t* offsets; int64_t n_total; const uint8_t* mask; const double* calm; int64_t calm_stride;
     const double* Rt2_in; const double* Rt3_in; const double* reconst0; int64_t B;
     double* Rt2; double* Rt3; double* reconst; int32_t* iter; double* repr_err; int32_t* used; int32_t* status;
+    int32_t loss = TFF_LOSS_NONE; double scale = 0.0; double* weight = nullptr;      // tff_bundle_adjust_loss_ragged_*
 };
 int check_ba_ragged(const void* corresp, const void* offsets, int64_t n_total, const void* calm, int64_t calm_stride, const void* Rt2_in, const void* Rt3_in,
                     int64_t B, const void* Rt2, const void* Rt3) {
@@ -1530,7 +1553,9 @@ int launch_ba_ragged(tff_ctx* c, const BaRaggedCall& q) {
     const size_t B = (size_t)q.B, nt = (size_t)q.n_total;
     // the plan: coff (B int64) | m (B) | class lists (3 B) | class counts (3);  a masked call: packed (6) | rec0 (3) | rec_ws (3 doubles) | src (int32) per correspondence
     TFF_TRY(c->ba_plan.reserve(B * sizeof(int64_t) + (4 * B + tff::BA_CLASSES) * sizeof(int32_t)));
-    if (q.mask) TFF_TRY(c->ba_pack.reserve(nt * (12 * sizeof(double) + sizeof(int32_t)) + 8));
+    // ... and, with a loss and a weight output, the compact weights (1 double)
+    const bool compact_w = q.mask && q.weight && q.loss != TFF_LOSS_NONE;
+    if (q.mask) TFF_TRY(c->ba_pack.reserve(nt * ((compact_w ? 13 : 12) * sizeof(double) + sizeof(int32_t)) + 8));
     tff::BaRaggedPlan p{};
     p.offsets = (const long*)q.offsets; p.B = (long)q.B; p.n_total = (long)q.n_total; p.mask = q.mask;
     // A launch lasts as long as its slowest item and the class launches follow one another on the stream, so classes pay only where a single launch
@@ -1546,11 +1571,13 @@ int launch_ba_ragged(tff_ctx* c, const BaRaggedCall& q) {
     p.cls_count = p.cls_list + tff::BA_CLASSES * B;
     p.corresp = q.corresp; p.reconst0 = q.reconst0;
     double* rec_ws = nullptr;
+    double* w_ws = nullptr;
     if (q.mask) {
         p.packed = (double*)c->ba_pack.p;
         p.rec0 = p.packed + 6 * nt;
         rec_ws = p.rec0 + 3 * nt;
-        p.src = (int*)(rec_ws + 3 * nt);
+        if (compact_w) w_ws = rec_ws + 3 * nt;
+        p.src = (int*)(rec_ws + (compact_w ? 4 : 3) * nt);
     }
     p.rec_ws = rec_ws;
     p.Rt2 = q.Rt2; p.Rt3 = q.Rt3; p.reconst = q.reconst; p.iter = q.iter; p.repr_err = q.repr_err; p.used = q.used; p.status = q.status;
@@ -1564,9 +1591,12 @@ int launch_ba_ragged(tff_ctx* c, const BaRaggedCall& q) {
         if (k > 0 && p.bound[k] == p.bound[k - 1]) continue;                 // (an empty class: the one-class plan)
         const tff::BaArgs a = tff::ba_ragged_class_args(p, q.calm, (long)q.calm_stride, q.Rt2_in, q.Rt3_in, rec_ws, k);
         const long grid = (k == 0 || q.B < BA_UPPER_CLASS_GRID) ? (long)tff::pose_grid(q.B) : BA_UPPER_CLASS_GRID;
-        TFF_TRY(launch(c, tff::k_bundle_adjust, (unsigned)grid, 64, tff::ba_lds_bytes(p.bound[k]), a));
+        if (q.loss == TFF_LOSS_NONE) TFF_TRY(launch(c, tff::k_bundle_adjust, (unsigned)grid, 64, tff::ba_lds_bytes(p.bound[k]), a));
+        else TFF_TRY(launch_ba_loss(c, q.loss, (unsigned)grid, tff::ba_lds_bytes(p.bound[k]),
+                                    tff::ba_ragged_class_loss_args(p, q.calm, (long)q.calm_stride, q.Rt2_in, q.Rt3_in, rec_ws, k, q.scale, w_ws, q.weight)));
     }
     if (q.reconst) TFF_TRY(launch(c, tff::k_ba_ragged_scatter, per_item, tff::BA_RAGGED_TILE, 0, p));
+    if (q.weight) TFF_TRY(launch(c, tff::k_ba_ragged_weight, per_item, tff::BA_RAGGED_TILE, 0, tff::BaRaggedWeights{p, w_ws, q.weight, q.loss == TFF_LOSS_NONE}));
     return 0;
 }
 
@@ -1629,10 +1659,19 @@ extern "C" {
 int tff_bundle_adjust_batch_dev(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in,
                                 const double* corresp, int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3,
                                 double* reconst, int32_t* iter, double* repr_err, int32_t* status) {
+    return tff_bundle_adjust_loss_batch_dev(c, calm, calm_stride, Rt2_in, Rt3_in, corresp, B, N, reconst0, Rt2, Rt3, reconst, iter, repr_err, status, TFF_LOSS_NONE, 0.0,
+                                            nullptr);
+}
+// ... with a robust loss and the weights (include/tftfund_loss.h); TFF_LOSS_NONE is the call above
+int tff_bundle_adjust_loss_batch_dev(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in,
+                                     const double* corresp, int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3,
+                                     double* reconst, int32_t* iter, double* repr_err, int32_t* status, int32_t loss, double scale, double* weight) {
     TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
     TFF_TRY(check_common(corresp, calm, calm_stride, B, N));
     return run_batch(c, B, Rt2_in && Rt3_in && Rt2 && Rt3, "null pose pointer", nullptr, [&] {
-        return launch_bundle_adjust(c, tff::BaArgs{calm, (long)calm_stride, Rt2_in, Rt3_in, corresp, (long)B, N, reconst0, Rt2, Rt3, reconst, iter, repr_err, status});
+        return launch_bundle_adjust(c, tff::BaArgs{calm, (long)calm_stride, Rt2_in, Rt3_in, corresp, (long)B, N, reconst0, Rt2, Rt3, reconst, iter, repr_err, status},
+                                    loss, scale, weight);
     });
 }
 
@@ -1640,7 +1679,14 @@ int tff_bundle_adjust_batch_dev(tff_ctx* c, const double* calm, int64_t calm_str
 int tff_bundle_adjust_batch_host(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in,
                                  const double* corresp, int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3,
                                  double* reconst, int32_t* iter, double* repr_err, int32_t* status) {
+    return tff_bundle_adjust_loss_batch_host(c, calm, calm_stride, Rt2_in, Rt3_in, corresp, B, N, reconst0, Rt2, Rt3, reconst, iter, repr_err, status, TFF_LOSS_NONE, 0.0,
+                                             nullptr);
+}
+int tff_bundle_adjust_loss_batch_host(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in,
+                                      const double* corresp, int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3,
+                                      double* reconst, int32_t* iter, double* repr_err, int32_t* status, int32_t loss, double scale, double* weight) {
     TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
     TFF_TRY(check_common(corresp, calm, calm_stride, B, N));
     return run_batch(c, B, Rt2_in && Rt3_in && Rt2 && Rt3, "null pose pointer", nullptr, [&] {
         const size_t nin = (size_t)B * 6 * (size_t)N * sizeof(double), npt = (size_t)B * 3 * (size_t)N * sizeof(double);
@@ -1652,8 +1698,11 @@ int tff_bundle_adjust_batch_host(tff_ctx* c, const double* calm, int64_t calm_st
         TFF_HIP(hipMemcpyAsync(s.poses_in, Rt2_in, npose, hipMemcpyHostToDevice, c->stream));
         TFF_HIP(hipMemcpyAsync(d_r3, Rt3_in, npose, hipMemcpyHostToDevice, c->stream));
         TFF_HIP(hipMemcpyAsync(s.calm, calm, ncal, hipMemcpyHostToDevice, c->stream));
+        const size_t nw = (size_t)B * (size_t)N * sizeof(double);
+        if (weight) TFF_TRY(c->ba_weight.reserve(nw));
         TFF_TRY(launch_bundle_adjust(c, tff::BaArgs{s.calm, (long)calm_stride, s.poses_in, d_r3, s.corresp, (long)B, N, s.reconst0, s.poses_out, d_o3, s.reconst,
-                                                    s.iter, s.repr_err, s.status}));
+                                                    s.iter, s.repr_err, s.status}, loss, scale, weight ? (double*)c->ba_weight.p : nullptr));
+        if (weight) TFF_HIP(hipMemcpyAsync(weight, c->ba_weight.p, nw, hipMemcpyDeviceToHost, c->stream));
         TFF_HIP(hipMemcpyAsync(Rt2, s.poses_out, npose, hipMemcpyDeviceToHost, c->stream));
         TFF_HIP(hipMemcpyAsync(Rt3, d_o3, npose, hipMemcpyDeviceToHost, c->stream));
         return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
@@ -1664,17 +1713,32 @@ int tff_bundle_adjust_batch_host(tff_ctx* c, const double* calm, int64_t calm_st
 int tff_bundle_adjust_ragged_dev(tff_ctx* c, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
                                  int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3,
                                  double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status) {
+    return tff_bundle_adjust_loss_ragged_dev(c, corresp, offsets, n_total, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, reconst, iter, repr_err, used,
+                                             status, TFF_LOSS_NONE, 0.0, nullptr);
+}
+int tff_bundle_adjust_loss_ragged_dev(tff_ctx* c, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
+                                      int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3,
+                                      double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status, int32_t loss, double scale,
+                                      double* weight) {
     TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
     TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2_in, Rt3_in, B, Rt2, Rt3));
     return run_batch(c, B, true, nullptr, &status, [&] {
         return launch_ba_ragged(c, BaRaggedCall{corresp, offsets, n_total, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, reconst, iter, repr_err,
-                                                used, status});
+                                                used, status, loss, scale, weight});
     });
 }
 int tff_bundle_adjust_ragged_host(tff_ctx* c, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm, int64_t calm_stride,
                                   const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3, double* reconst,
                                   int32_t* iter, double* repr_err, int32_t* used, int32_t* status) {
+    return tff_bundle_adjust_loss_ragged_host(c, corresp, offsets, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, reconst, iter, repr_err, used, status,
+                                              TFF_LOSS_NONE, 0.0, nullptr);
+}
+int tff_bundle_adjust_loss_ragged_host(tff_ctx* c, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm, int64_t calm_stride,
+                                       const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3, double* reconst,
+                                       int32_t* iter, double* repr_err, int32_t* used, int32_t* status, int32_t loss, double scale, double* weight) {
     TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
     if (B < 0) return fail(TFF_E_INVALID, "negative batch size");
     if (B > 0 && !offsets) return fail(TFF_E_INVALID, "null pointer");
     if (B > 0 && offsets[0] < 0) return fail(TFF_E_INVALID, "offsets[0] must be >= 0");
@@ -1691,6 +1755,8 @@ int tff_bundle_adjust_ragged_host(tff_ctx* c, const double* corresp, const int64
         TFF_TRY(c->idx.reserve(nb * 2 * sizeof(int32_t)));
         TFF_TRY(c->ragged_off.reserve((nb + 1) * sizeof(int64_t)));
         TFF_TRY(c->ba_host.reserve(nb * sizeof(int32_t) + nt + 8));
+        if (weight) TFF_TRY(c->ba_weight.reserve(nt * sizeof(double) + 8));
+        double* d_w = weight ? (double*)c->ba_weight.p : nullptr;
         double* d_in = (double*)c->in.p;
         double* d_x0 = d_in + 6 * nt;
         double* d_r2 = d_x0 + 3 * nt;
@@ -1710,7 +1776,9 @@ int tff_bundle_adjust_ragged_host(tff_ctx* c, const double* corresp, const int64
         TFF_HIP(hipMemcpyAsync(c->calm.p, calm, ncal, hipMemcpyHostToDevice, c->stream));
         TFF_HIP(hipMemcpyAsync(c->ragged_off.p, offsets, (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         TFF_TRY(launch_ba_ragged(c, BaRaggedCall{d_in, (const int64_t*)c->ragged_off.p, n_total, mask ? d_mask : nullptr, (const double*)c->calm.p, calm_stride, d_r2, d_r3,
-                                                 reconst0 ? d_x0 : nullptr, B, d_o2, d_o3, reconst ? d_rec : nullptr, d_iter, d_err, d_used, d_iter + nb}));
+                                                 reconst0 ? d_x0 : nullptr, B, d_o2, d_o3, reconst ? d_rec : nullptr, d_iter, d_err, d_used, d_iter + nb,
+                                                 loss, scale, d_w}));
+        if (weight && cnt) TFF_HIP(hipMemcpyAsync(weight + f, d_w + f, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         TFF_HIP(hipMemcpyAsync(Rt2, d_o2, npose, hipMemcpyDeviceToHost, c->stream));
         TFF_HIP(hipMemcpyAsync(Rt3, d_o3, npose, hipMemcpyDeviceToHost, c->stream));
         if (reconst && cnt) TFF_HIP(hipMemcpyAsync(reconst + 3 * f, d_rec + 3 * f, cnt * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
