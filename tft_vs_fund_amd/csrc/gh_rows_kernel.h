@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(64, 2) k_gh_linear_rows(const GhWgArgs a) {
             } else {
                 double cen[6], nr[9];
                 rows_centroids(src, N, cen);
-                rows_distances_moments(src, N, cen, w->nrm, nr, w->mom);
+                rows_distances_moments(src, N, cen, w->nrm, nr, w->mom, w->ov);
             }
             wave_sync();
             const bool ok = rows_linear_tft_middle(w, nullptr, true);

@@ -22,6 +22,7 @@
 #include "tft_moments_kernel.h"
 #include <rows_target.h>
 #include <regs_target.h>
+#include <moments_target.h>
 
 namespace tff {
 
@@ -128,7 +129,7 @@ __device__ __forceinline__ void rows_centroids(const RowSrc& s, const int N, dou
 //     {y1^2, y1, 1} (96 accumulators per lane would not fit the register file; 48 each do, and the pair's loads coalesce into one request);
 //   * the pair also splits the distance sums: even lane view 1, odd lane view 3, view 2 alternately (two correspondences per loop iteration).
 // Leaves nrm[0..8] (LDS, and nr[] on every lane) and mom[0..95] (LDS).
-__device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const int N, const double (&c)[6], double* nrm, double (&nr)[9], double* mom) {
+__device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const int N, const double (&c)[6], double* nrm, double (&nr)[9], double* mom, double* ov) {
     const int p = rows_p();
     const int slot = p >> 1;
     const bool odd = (p & 1) != 0;
@@ -136,15 +137,17 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
 #pragma unroll
     for (int k = 0; k < 48; ++k) acc[k] = zero_f64();                        // (one 64-bit move each: regs_target.h)
     double dA = 0.0, dB = 0.0;
-    // (the loads of trips t + 1 and t + 2 are in flight while trip t is consumed: a trip issues ~80 fp64 instructions, an L2 / MALL round trip
-    // lasts five times that, and the other wavefront of the SIMD is in the same pass more often than not)
+    // (the loads of trip t + 1 are in flight while trip t is consumed, ~170 fp64 instructions; what an L2 / MALL round trip lasts beyond that is
+    // left to the other wavefront of the SIMD, which is in the same pass more often than not)
     // (view 2's distance is needed once per correspondence and the pair holds two of them per loop iteration: the even lane takes the first one's
     // square root, the odd lane the second one's -- three square roots per lane and two trips instead of four)
     auto body = [&](const Pt6& q, double& r2_out) {
         const double x1 = q.v[0] - c[0], y1 = q.v[1] - c[1];
         const double x2 = q.v[2] - c[2], y2 = q.v[3] - c[3];
         const double x3 = q.v[4] - c[4], y3 = q.v[5] - c[5];
-        const double r1 = x1 * x1 + y1 * y1, r2 = x2 * x2 + y2 * y2, r3 = x3 * x3 + y3 * y3;
+        // (a sum of two products has two fused forms, and which one the compiler picks follows the shape of the code around it: the form it has
+        // always picked here, fma(y, y, x * x), is written out -- moments_target.h::sum_sq_yx -- so that the unrolled loop below keeps the bits)
+        const double r1 = sum_sq_yx(x1, y1), r2 = sum_sq_yx(x2, y2), r3 = sum_sq_yx(x3, y3);
         dA += sqrt_nonneg_uniform(odd ? r3 : r1);                            // Normalize2Ddata.m:35
         r2_out = r2;
         const double q2[4] = {1.0, x2, y2, r2};
@@ -161,20 +164,27 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
             }
     };
     constexpr int STEP = ROWL / 2;
-    Pt6 pe = rows_load(s, (slot < N) ? slot : 0);
-    Pt6 po = rows_load(s, (slot + STEP < N) ? slot + STEP : 0);
-#pragma unroll 1
-    for (int i = slot; i < N; i += 2 * STEP) {
-        const Pt6 q = pe;
-        if (i + 2 * STEP < N) pe = rows_load(s, i + 2 * STEP);
+    // One trip: the two correspondences of the pair at i and i + STEP from (ce, co), the next trip's loads into (ne, no).  The loop alternates
+    // between two pairs of buffers, so that a trip's points stay where their loads put them: rotating one pair through copies (q = pe; pe = load)
+    // cost two 12-register moves per trip.  Same loads, at the same places in the instruction stream; same arithmetic in the same order.
+    auto trip = [&](const Pt6& ce, const Pt6& co, Pt6& ne, Pt6& no, const int i) {
+        loads_landed(ce.v);                                                  // (the copies used to wait here: the next trip's loads go out behind this trip's and have the
+        loads_landed(co.v);                                                  //  whole trip to arrive)
+        if (i + 2 * STEP < N) ne = rows_load(s, i + 2 * STEP);
+        if (i + 3 * STEP < N) no = rows_load(s, i + 3 * STEP);
         double r2a, r2b = 0.0;
-        body(q, r2a);
-        if (i + STEP < N) {
-            const Pt6 r = po;
-            if (i + 3 * STEP < N) po = rows_load(s, i + 3 * STEP);
-            body(r, r2b);
-        }
+        body(ce, r2a);
+        if (i + STEP < N) body(co, r2b);
         dB += sqrt_nonneg_uniform(odd ? r2b : r2a);
+    };
+    Pt6 ae = rows_load(s, (slot < N) ? slot : 0);
+    Pt6 ao = rows_load(s, (slot + STEP < N) ? slot + STEP : 0);
+    Pt6 be = ae, bo = ao;                                                    // (never read before a trip has loaded them)
+#pragma unroll 1
+    for (int i0 = 0; i0 < N; i0 += 4 * STEP) {                               // (wave-uniform control; a pair past the end sits a trip out)
+        if (i0 + slot < N) trip(ae, ao, be, bo, i0 + slot);
+        if (i0 + 2 * STEP >= N) break;
+        if (i0 + 2 * STEP + slot < N) trip(be, bo, ae, ao, i0 + 2 * STEP + slot);
     }
     // mean distances -> scales and offsets (every lane of the row)
     const double d1 = row_sum16(odd ? 0.0 : dA), d3 = row_sum16(odd ? dA : 0.0), d2 = row_sum16(dB);
@@ -191,26 +201,41 @@ __device__ __forceinline__ void rows_distances_moments(const RowSrc& s, const in
 #pragma unroll
         for (int k = 0; k < 9; ++k) nrm[k] = nr[k];
     }
-    // sums over the eight lanes of equal parity: halving butterfly (masks 8, 4, 2), 48 -> 6 values per lane
-    const bool up8 = (p & 8) != 0, up4 = (p & 4) != 0, up2 = (p & 2) != 0;   // (once for the 42 steps)
-#pragma unroll
-    for (int i = 0; i < 24; ++i) acc[i] = halve_sum<8>(acc[i], acc[i + 24], up8);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = halve_sum<4>(acc[i], acc[i + 12], up4);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) acc[i] = halve_sum<2>(acc[i], acc[i + 6], up2);
-    // the lane holds local indices base .. base + 5 of its parity's 48 sums; global moment index 48 * parity + local = 16 h + 4 i3 + i2
-    const int base = 6 * ((p >> 1) & 1) + 12 * ((p >> 2) & 1) + 24 * ((p >> 3) & 1);
+    // Sums over the eight lanes of equal parity, through the row's overlay (free until the first eigen-solve) instead of a halving butterfly over
+    // the registers: no keep / send select and no DPP move, 42 additions as before.  Three chunks of 16 accumulators per lane (16 lanes x 18 doubles:
+    // the overlay holds 380); a lane's chunk starts 144 bytes after its neighbour's -- 16-byte aligned for the paired accesses, and not the 128 bytes
+    // that would put all sixteen lanes on the same banks.  Position p then sums, for its parity, local indices 16 c + 2 (p >> 1) + {0, 1} of chunk c
+    // over the eight lanes m = 0 .. 7 of that parity in the butterfly's tree: lanes 8 apart first, then 4, then 2 --
+    // ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7)) with m = lane >> 1; which lane of a pair is the left operand does not change a sum.
+    constexpr int CH = 16, LSTRIDE = CH + 2;
+    static_assert(48 % CH == 0 && ROWL * LSTRIDE <= ROW_OV_DOUBLES && (LSTRIDE * sizeof(double)) % 16 == 0, "chunks fit the overlay, pairs stay aligned");
+    const int par = p & 1;
+    Pair16* const mine = reinterpret_cast<Pair16*>(ov + LSTRIDE * p);
+    const double* const theirs = ov + LSTRIDE * par + 2 * (p >> 1);
+    // global moment index e = 48 * parity + local = 16 h + 4 i3 + i2: i3 and i2 follow from the position alone, h = 3 * parity + c
+    // degrees: p1 = {x^2, xy, x, y^2, y, 1} -> {2,2,1,2,1,0};  q = {1, x, y, x^2+y^2} -> {0,1,1,2}
     const double s1 = nr[0], s2 = nr[3], s3 = nr[6];
+    const int i3 = (p >> 2) & 3;
+    const bool i2hi = ((p >> 1) & 1) != 0;                                   // i2 = 2 * i2hi + t
+    const double f3 = (i3 == 0) ? 1.0 : ((i3 == 3) ? s3 * s3 : s3);
+    const double f2[2] = {i2hi ? s2 : 1.0, i2hi ? s2 * s2 : s2};
+    const double f1c[3] = {s1 * s1, par ? s1 : s1 * s1, par ? 1.0 : s1};     // h = 0 / 3, 1 / 4, 2 / 5
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int e = 48 * (p & 1) + base + i;
-        const int h = e >> 4, i3 = (e >> 2) & 3, i2 = e & 3;
-        // degrees: p1 = {x^2, xy, x, y^2, y, 1} -> {2,2,1,2,1,0};  q = {1, x, y, x^2+y^2} -> {0,1,1,2}
-        const double f1 = (h == 5) ? 1.0 : ((h == 2 || h == 4) ? s1 : s1 * s1);
-        const double f3 = (i3 == 0) ? 1.0 : ((i3 == 3) ? s3 * s3 : s3);
-        const double f2 = (i2 == 0) ? 1.0 : ((i2 == 3) ? s2 * s2 : s2);
-        mom[e] = acc[i] * (f1 * f3 * f2);
+    for (int c = 0; c < 48 / CH; ++c) {
+        if (c > 0) wave_sync();                                              // the previous chunk has been read
+#pragma unroll
+        for (int k = 0; k < CH; k += 2) { Pair16 v; v[0] = acc[CH * c + k]; v[1] = acc[CH * c + k + 1]; mine[k / 2] = v; }
+        wave_sync();
+        double v[8][2];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) load_pairs16<2>(theirs + 2 * LSTRIDE * m, v[m]);
+        Pair16 out;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const double sum = ((v[0][t] + v[4][t]) + (v[2][t] + v[6][t])) + ((v[1][t] + v[5][t]) + (v[3][t] + v[7][t]));
+            out[t] = sum * (f1c[c] * f3 * f2[t]);
+        }
+        *reinterpret_cast<Pair16*>(mom + 48 * par + CH * c + 2 * (p >> 1)) = out;
     }
 }
 
@@ -1098,7 +1123,7 @@ __global__ void __launch_bounds__(64, 2) k_linear_tft_pose_rows(const LinearTftA
                 double cen[6], nr[9];
                 rows_centroids(j.src, N, cen);                               // LinearTFTPoseEstimation.m:45-47
                 rows_stamp(dbg, 1);
-                rows_distances_moments(j.src, N, cen, w->nrm, nr, w->mom);
+                rows_distances_moments(j.src, N, cen, w->nrm, nr, w->mom, w->ov);
                 if (dbg && p < 9) dbg[71 + p] = w->nrm[p];
             }
             wave_sync();
