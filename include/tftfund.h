@@ -325,6 +325,8 @@ int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]);
 /* Declared in tftfund_loss.h, which this header includes at its end: robust losses (Huber, Cauchy) for the three-view bundle adjustment.
  * tff_bundle_adjust_loss_batch_dev / _host and tff_bundle_adjust_loss_ragged_dev / _host take the arguments of the four tff_bundle_adjust_batch_* and
  * tff_bundle_adjust_ragged_* calls above plus `int32_t loss, double scale, double* weight` at the end.  With TFF_LOSS_NONE they are those calls, bit for bit. */
+/* Declared in tftfund_cov.h, included at the end as well: the covariance of the adjusted poses and points.  tff_ba_covariance_batch_* / _ragged_* evaluate it at
+ * given poses and points; tff_bundle_adjust_cov_batch_* / _ragged_* are the loss forms followed by it, with `double* cov, double* sigma0, double* point_cov`. */
 
 /* BundleAdjustment (Optimization/BundleAdjustment.m:49-216) as the reference writes it, for M = 2 .. 6 views, in MATLAB's own
  * array layouts so that a gateway passes its arguments through: calm = CalM (3M x 3, column-major; calm_stride 0 = shared, 9M =
@@ -531,5 +533,6 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 #endif
 #include "tftfund_adaptive.h"   /* entry points added after library version 103 */
 #include "tftfund_guided.h"     /* entry points added after library version 104 */
+#include "tftfund_cov.h"        /* entry points added after library version 106 (its loss codes are those of the header below) */
 #include "tftfund_loss.h"       /* entry points added after library version 105 */
 #endif

@@ -140,9 +140,17 @@ def load_library(path=None):
             "tff_bundle_adjust_loss_batch_host": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
             "tff_bundle_adjust_loss_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V],
             "tff_bundle_adjust_loss_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_ba_covariance_batch_dev": [V, V, I64, V, V, V, I64, I32, V, I32, F64, V, V, V],
+            "tff_ba_covariance_batch_host": [V, V, I64, V, V, V, I64, I32, V, I32, F64, V, V, V],
+            "tff_ba_covariance_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, I32, F64, V, V, V],
+            "tff_ba_covariance_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, I32, F64, V, V, V],
+            "tff_bundle_adjust_cov_batch_dev": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
+            "tff_bundle_adjust_cov_batch_host": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
+            "tff_bundle_adjust_cov_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
+            "tff_bundle_adjust_cov_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -198,6 +206,9 @@ GUIDED_SYMBOLS = ["tff_robust_pose_scenes_guided_dev", "tff_robust_pose_scenes_g
 LOSS_SYMBOLS = ["tff_bundle_adjust_loss_batch_dev", "tff_bundle_adjust_loss_batch_host", "tff_bundle_adjust_loss_ragged_dev",
                 "tff_bundle_adjust_loss_ragged_host"]
 LOSS_IDS = {"huber": 1, "cauchy": 2}      # include/tftfund_loss.h TFF_LOSS_*; 0 is TFF_LOSS_NONE
+# ... and every symbol include/tftfund_cov.h declares: the entry points added after library version 106 (covariances of the bundle adjustment)
+COV_SYMBOLS = ["tff_ba_covariance_batch_dev", "tff_ba_covariance_batch_host", "tff_ba_covariance_ragged_dev", "tff_ba_covariance_ragged_host",
+               "tff_bundle_adjust_cov_batch_dev", "tff_bundle_adjust_cov_batch_host", "tff_bundle_adjust_cov_ragged_dev", "tff_bundle_adjust_cov_ragged_host"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -402,6 +413,31 @@ def order_from_quality(quality, offsets):
     glob = by_q[np.argsort(scene[by_q], kind="stable")]
     sg = scene[glob]
     return np.where((sg >= 0) & (sg < S), glob - off[np.clip(sg, 0, S)], -1).astype(np.int32)
+
+
+def euler_cov_to_rotvec(R_t_2, R_t_3, cov):
+    """The covariance of a bundle adjustment (bundle_adjust(..., cov=True), ba_covariance: parameters angles2, angles3, t2, t3 with the angles of
+    R = Rx(a) Ry(b) Rz(c), BundleAdjustment.m:92-94) in LEFT-PERTURBATION ROTATION-VECTOR coordinates: parameters omega2, omega3, t2, t3 with
+    R(angles + d) = exp([omega]x) R(angles) to first order, omega = e_x da + Rx e_y db + Rx Ry e_z dc.  sqrt of the trace of a 3 x 3 rotation block is
+    then the rotation's standard deviation in radians, whatever the angles are.  Host helper, numpy: R_t_2, R_t_3 (3,4) or (B,3,4), cov (12,12) or
+    (B,12,12) -> the same shape."""
+    to_np = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    r2, r3, cv = to_np(R_t_2), to_np(R_t_3), to_np(cov)
+    single = cv.ndim == 2
+    if single:
+        r2, r3, cv = r2[None], r3[None], cv[None]
+    if r2.shape[1:] != (3, 4) or r3.shape != r2.shape or cv.shape != (r2.shape[0], 12, 12):
+        raise ValueError("R_t_2, R_t_3 must be (B, 3, 4) and cov (B, 12, 12)")
+    out = np.empty_like(cv)
+    for b in range(cv.shape[0]):
+        T = np.eye(12)
+        for j, R in enumerate((r2[b][:, :3], r3[b][:, :3])):
+            a = -np.arctan2(R[1, 2], R[2, 2]); bb = -np.arctan2(-R[0, 2], np.hypot(R[1, 2], R[2, 2]))
+            ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(bb), np.sin(bb)
+            Rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]]); Ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]])
+            T[3 * j:3 * j + 3, 3 * j:3 * j + 3] = np.stack([np.array([1.0, 0, 0]), Rx[:, 1], (Rx @ Ry)[:, 2]], axis=1)
+        out[b] = T @ cv[b] @ T.T
+    return out[0] if single else out
 
 
 def pack_ragged(items):
@@ -808,12 +844,15 @@ class Context:
                                                          self._p(it), self._p(st)), "tff_linear_f_batch_dev")
         return F21.reshape(B, 3, 3).transpose(1, 2), F31.reshape(B, 3, 3).transpose(1, 2), it, st
 
-    def bundle_adjust(self, calm, R_t_2, R_t_3, corresp, reconst0=None, loss=None, scale=None):
+    def bundle_adjust(self, calm, R_t_2, R_t_3, corresp, reconst0=None, loss=None, scale=None, cov=False, point_cov=False):
         """BundleAdjustment for B triplets: calm (9,3) or (B,9,3); R_t_2, R_t_3 (B,3,4); corresp (B,N,6); reconst0 (B,3,N) or None.
         -> dict(R_t_2, R_t_3 (B,3,4), Reconst (B,3,N), iter, repr_err, status).
         loss = "huber" or "cauchy" with scale = c in pixels (tff_bundle_adjust_loss_batch_dev, include/tftfund_loss.h): the adjustment minimises
         sum rho(|pixel residual|^2) by reweighted Levenberg-Marquardt, repr_err is the square root of that sum, and weight (B,N), rho' at the final
-        parameters, joins the dict.  Without a loss nothing changes."""
+        parameters, joins the dict.  Without a loss nothing changes.
+        cov=True (tff_bundle_adjust_cov_batch_dev, include/tftfund_cov.h): cov (B,12,12), the covariance of (angles2, angles3, t2, t3) in the gauge
+        |t2| = 1, and sigma0 (B,) join the dict; point_cov=True adds them and point_cov (B,N,6), every point's 3x3 block packed xx xy xz yy yz zz.
+        They are what ba_covariance gives on this call's outputs, and every other output keeps its bits."""
         robust = _check_loss(loss, scale)
         self._begin()
         corresp = self._t(corresp); B, N, _ = corresp.shape
@@ -833,14 +872,49 @@ class Context:
              self._p(it), self._p(err), self._p(st))
         out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec.transpose(1, 2),
                    iter=it, repr_err=err, status=st)
-        if robust is None:
+        if robust is not None:
+            out["weight"] = torch.empty((B, N), dtype=torch.float64, device=dev)
+        if cov or point_cov:
+            out["cov"] = torch.empty((B, 12, 12), dtype=torch.float64, device=dev); out["sigma0"] = torch.empty(B, dtype=torch.float64, device=dev)
+            if point_cov:
+                out["point_cov"] = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+            _check(self.lib, self.lib.tff_bundle_adjust_cov_batch_dev(*a, *(robust or (0, 0.0)), self._p(out.get("weight")), self._p(out["cov"]), self._p(out["sigma0"]),
+                                                                      self._p(out.get("point_cov"))), "tff_bundle_adjust_cov_batch_dev")
+        elif robust is None:
             _check(self.lib, self.lib.tff_bundle_adjust_batch_dev(*a), "tff_bundle_adjust_batch_dev")
         else:
-            out["weight"] = torch.empty((B, N), dtype=torch.float64, device=dev)
             _check(self.lib, self.lib.tff_bundle_adjust_loss_batch_dev(*a, robust[0], robust[1], self._p(out["weight"])), "tff_bundle_adjust_loss_batch_dev")
         return out
 
-    def bundle_adjust_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, mask=None, reconst0=None, reconst=True, loss=None, scale=None):
+    def ba_covariance(self, calm, R_t_2, R_t_3, corresp, reconst, loss=None, scale=None, point_cov=False):
+        """The covariance of a three-view bundle adjustment AT the given poses and points (tff_ba_covariance_batch_dev, include/tftfund_cov.h; no
+        iteration is run): calm (9,3) or (B,9,3); R_t_2, R_t_3 (B,3,4); corresp (B,N,6); reconst (B,3,N), as bundle_adjust takes and returns them;
+        loss, scale as there.  -> dict(cov (B,12,12), sigma0 (B,)[, point_cov (B,N,6)]): cov is that of (angles2, angles3, t2, t3) -- the angles of
+        R = Rx Ry Rz, see euler_cov_to_rotvec -- in the gauge |t2| = 1, sigma0^2 = r'r / (3N - 11) (normalised units without a loss, pixels with
+        one); NaN for N <= 3 and for non-finite poses."""
+        robust = _check_loss(loss, scale) or (0, 0.0)
+        self._begin()
+        corresp = self._t(corresp); B, N, _ = corresp.shape
+        dev = corresp.device
+        calm = self._t(calm)
+        if calm.dim() == 2:
+            calm_cm, stride = calm.t().contiguous().reshape(27), 0
+        else:
+            calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(B * 27), 27
+        r2 = self._cams_cm(self._t(R_t_2)); r3 = self._cams_cm(self._t(R_t_3))
+        x = self._t(reconst).transpose(1, 2).contiguous()
+        if tuple(x.shape) != (B, N, 3):
+            raise ValueError("reconst must be (B, 3, N)")
+        out = dict(cov=torch.empty((B, 12, 12), dtype=torch.float64, device=dev), sigma0=torch.empty(B, dtype=torch.float64, device=dev))
+        if point_cov:
+            out["point_cov"] = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+        _check(self.lib, self.lib.tff_ba_covariance_batch_dev(self.handle, self._p(calm_cm), stride, self._p(r2), self._p(r3), self._p(corresp), B, N, self._p(x),
+                                                              robust[0], robust[1], self._p(out["cov"]), self._p(out["sigma0"]), self._p(out.get("point_cov"))),
+               "tff_ba_covariance_batch_dev")
+        return out
+
+    def bundle_adjust_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, mask=None, reconst0=None, reconst=True, loss=None, scale=None, cov=False,
+                             point_cov=False, _cov_only=None):
         """BundleAdjustment for B items with different correspondence counts in one call (tff_bundle_adjust_ragged_*): corresp (Ntot, 6) packed,
         offsets (B + 1,) int64 with item b = corresp[offsets[b]:offsets[b + 1]] (see pack_ragged), mask None or (Ntot,) uint8 / bool (non-zero = use the
         correspondence: the `mask` of robust_pose_scenes), calm (9, 3) or (B, 9, 3), R_t_2, R_t_3 (B, 3, 4), reconst0 None or (Ntot, 3) (read where
@@ -849,8 +923,11 @@ class Context:
         Returns dict(R_t_2, R_t_3 (B,3,4), Reconst (Ntot,3) or None -- NaN where not selected --, iter, repr_err, used, status (B,)); per item
         ST_BAD_OFFSETS / ST_TOO_FEW (nothing selected) / ST_TOO_LARGE (more than BA_MAX_N selected) with NaN poses.
         loss, scale: as bundle_adjust (tff_bundle_adjust_loss_ragged_*); weight (Ntot,), packed like corresp, joins the dict: NaN where the mask
-        deselects and over an item that failed.  Item b still equals bundle_adjust with the same loss on its selection, bit for bit."""
+        deselects and over an item that failed.  Item b still equals bundle_adjust with the same loss on its selection, bit for bit.
+        cov, point_cov: as bundle_adjust (tff_bundle_adjust_cov_ragged_*): cov (B,12,12), sigma0 (B,) and point_cov (Ntot,6), packed like corresp and NaN
+        where not selected; NaN for an item that failed or has three or fewer selected.  They are ba_covariance_ragged on this call's outputs."""
         robust = _check_loss(loss, scale)
+        want_cov = bool(cov or point_cov)
         host = isinstance(corresp, np.ndarray)
         if host:
             offsets = np.asarray(offsets)
@@ -877,7 +954,7 @@ class Context:
         if mask is not None and tuple(mask.shape) != (ntot,):
             raise ValueError("mask must hold one flag per packed correspondence: (%d,)" % ntot)
         if reconst0 is not None and tuple(reconst0.shape) != (ntot, 3):
-            raise ValueError("reconst0 must be (Ntot, 3), packed like corresp")
+            raise ValueError("%s must be (Ntot, 3), packed like corresp" % ("reconst0" if _cov_only is None else "reconst"))
         if not isinstance(calm, (np.ndarray, torch.Tensor)) or tuple(calm.shape) not in ((9, 3), (B, 9, 3)):
             raise ValueError("CalM must be a (9, 3) or (B, 9, 3) array or tensor")
         if host:
@@ -894,10 +971,25 @@ class Context:
                  ptr(err), ptr(used), ptr(st))
             out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(0, 2, 1), R_t_3=o3.reshape(B, 4, 3).transpose(0, 2, 1), Reconst=rec, iter=it, repr_err=err,
                        used=used, status=st)
-            if robust is None:
+            if _cov_only is not None:                                        # ba_covariance_ragged: the same arguments, no adjustment
+                co = dict(cov=np.full((B, 12, 12), np.nan), sigma0=np.full(B, np.nan))
+                if _cov_only:
+                    co["point_cov"] = np.full((ntot, 6), np.nan)
+                _check(self.lib, self.lib.tff_ba_covariance_ragged_host(self.handle, ptr(corresp), ptr(offsets), ptr(mk), ptr(calm_cm), stride, ptr(r2), ptr(r3), ptr(x0), B,
+                                                                        *(robust or (0, 0.0)), ptr(co["cov"]), ptr(co["sigma0"]), ptr(co.get("point_cov"))),
+                       "tff_ba_covariance_ragged_host")
+                return co
+            if robust is not None:
+                out["weight"] = np.full(ntot, np.nan)
+            if want_cov:
+                out["cov"] = np.full((B, 12, 12), np.nan); out["sigma0"] = np.full(B, np.nan)
+                if point_cov:
+                    out["point_cov"] = np.full((ntot, 6), np.nan)
+                _check(self.lib, self.lib.tff_bundle_adjust_cov_ragged_host(*a, *(robust or (0, 0.0)), ptr(out.get("weight")), ptr(out["cov"]), ptr(out["sigma0"]),
+                                                                            ptr(out.get("point_cov"))), "tff_bundle_adjust_cov_ragged_host")
+            elif robust is None:
                 _check(self.lib, self.lib.tff_bundle_adjust_ragged_host(*a), "tff_bundle_adjust_ragged_host")
             else:
-                out["weight"] = np.full(ntot, np.nan)
                 _check(self.lib, self.lib.tff_bundle_adjust_loss_ragged_host(*a, robust[0], robust[1], ptr(out["weight"])), "tff_bundle_adjust_loss_ragged_host")
             return out
         dev = corresp.device
@@ -915,12 +1007,39 @@ class Context:
              self._p(o2), self._p(o3), self._p(rec), self._p(it), self._p(err), self._p(used), self._p(st))
         out = dict(R_t_2=o2.reshape(B, 4, 3).transpose(1, 2), R_t_3=o3.reshape(B, 4, 3).transpose(1, 2), Reconst=rec, iter=it, repr_err=err, used=used,
                    status=st)
-        if robust is None:
+        nans = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        if _cov_only is not None:                                            # ba_covariance_ragged: the same arguments, no adjustment
+            co = dict(cov=nans(B, 12, 12), sigma0=nans(B))
+            if _cov_only:
+                co["point_cov"] = nans(ntot, 6)
+            _check(self.lib, self.lib.tff_ba_covariance_ragged_dev(self.handle, self._p(corresp), self._p(offsets), ntot, self._p(mk), self._p(calm_cm), stride, self._p(r2),
+                                                                   self._p(r3), self._p(x0), B, *(robust or (0, 0.0)), self._p(co["cov"]), self._p(co["sigma0"]),
+                                                                   self._p(co.get("point_cov"))), "tff_ba_covariance_ragged_dev")
+            return co
+        if robust is not None:
+            out["weight"] = nans(ntot)
+        if want_cov:
+            out["cov"] = nans(B, 12, 12); out["sigma0"] = nans(B)
+            if point_cov:
+                out["point_cov"] = nans(ntot, 6)
+            _check(self.lib, self.lib.tff_bundle_adjust_cov_ragged_dev(*a, *(robust or (0, 0.0)), self._p(out.get("weight")), self._p(out["cov"]), self._p(out["sigma0"]),
+                                                                       self._p(out.get("point_cov"))), "tff_bundle_adjust_cov_ragged_dev")
+        elif robust is None:
             _check(self.lib, self.lib.tff_bundle_adjust_ragged_dev(*a), "tff_bundle_adjust_ragged_dev")
         else:
-            out["weight"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
             _check(self.lib, self.lib.tff_bundle_adjust_loss_ragged_dev(*a, robust[0], robust[1], self._p(out["weight"])), "tff_bundle_adjust_loss_ragged_dev")
         return out
+
+    def ba_covariance_ragged(self, calm, R_t_2, R_t_3, corresp, offsets, reconst, mask=None, loss=None, scale=None, point_cov=False):
+        """ba_covariance for B items with different correspondence counts in one call (tff_ba_covariance_ragged_*): the arguments of
+        bundle_adjust_ragged, with reconst (Ntot, 3) the points, packed like corresp and read where selected -- what bundle_adjust_ragged returns as
+        Reconst.  -> dict(cov (B,12,12), sigma0 (B,)[, point_cov (Ntot,6), NaN where not selected]).  Item b gets bit for bit what ba_covariance gives
+        for its selected correspondences alone; an item with bad offsets, nothing or too little (three or fewer) selected, or NaN poses gets NaN.
+        CUDA tensors in -> CUDA tensors out, no synchronisation; numpy in -> numpy out through the _host form."""
+        if reconst is None:
+            raise ValueError("the covariance is evaluated at given points: reconst must be (Ntot, 3)")
+        return self.bundle_adjust_ragged(calm, R_t_2, R_t_3, corresp, offsets, mask=mask, reconst0=reconst, reconst=False, loss=loss, scale=scale,
+                                         _cov_only=bool(point_cov))
 
     @staticmethod
     def _refined(out, r):
@@ -928,25 +1047,29 @@ class Context:
         out.update(R_t_2_refined=r["R_t_2"], R_t_3_refined=r["R_t_3"], T_refined=r["T"], iter_refined=r["iter"], status_refined=r["status"])
 
     @staticmethod
-    def _check_polish(polish_loss, polish_scale, polish_all, threshold):
-        """the polish arguments of the robust calls -> (loss, scale, all matches)"""
+    def _check_polish(polish_loss, polish_scale, polish_all, threshold, polish=True, polish_cov=False):
+        """the polish arguments of the robust calls -> (loss, scale, all matches, with the covariance)"""
         robust = _check_loss(polish_loss, polish_scale, "polish_loss", threshold)
         if polish_all and robust is None:
             raise ValueError("polish_all=True adjusts over all matches of a scene, wrong ones included: it needs a polish_loss")
-        return (polish_loss, None if robust is None else robust[1], bool(polish_all))
+        if polish_cov and not polish:
+            raise ValueError("polish_cov=True is the covariance of the polished pose: it needs polish=True")
+        return (polish_loss, None if robust is None else robust[1], bool(polish_all), bool(polish_cov))
 
-    def _polish(self, out, calm, scenes, offsets, single, how=(None, None, False)):
+    def _polish(self, out, calm, scenes, offsets, single, how=(None, None, False, False)):
         """the polish of robust_pose / robust_pose_scenes: ONE bundle_adjust_ragged call on the result's poses and mask (how: _check_polish -- with a
         loss, and then over the mask or over all matches)"""
         r2, r3 = out["R_t_2"], out["R_t_3"]
         if single:
             r2, r3 = r2[None], r3[None]
-        ba = self.bundle_adjust_ragged(calm, r2, r3, scenes, offsets, mask=None if how[2] else out["mask"], reconst=False, loss=how[0], scale=how[1])
+        ba = self.bundle_adjust_ragged(calm, r2, r3, scenes, offsets, mask=None if how[2] else out["mask"], reconst=False, loss=how[0], scale=how[1], cov=how[3])
         pick = (lambda a: a[0]) if single else (lambda a: a)
         out.update(R_t_2_polished=pick(ba["R_t_2"]), R_t_3_polished=pick(ba["R_t_3"]), iter_polished=pick(ba["iter"]),
                    repr_err_polished=pick(ba["repr_err"]), status_polished=pick(ba["status"]))
         if how[0] is not None:
             out["weight_polished"] = ba["weight"]                            # packed like mask
+        if how[3]:
+            out.update(cov_polished=pick(ba["cov"]), sigma0_polished=pick(ba["sigma0"]))
         return out
 
     def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None):
@@ -1053,7 +1176,8 @@ class Context:
         return (mask, cnt) if with_counts else mask
 
     def robust_pose(self, method, scene, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, refine=None, polish=False,
-                    confidence=None, first_round=256, order=None, quality=None, growth=200000, polish_loss=None, polish_scale=None, polish_all=False):
+                    confidence=None, first_round=256, order=None, quality=None, growth=200000, polish_loss=None, polish_scale=None, polish_all=False,
+                    polish_cov=False):
         """Pose from matches with outliers (tff_robust_pose_*): n_hyp minimal-sample hypotheses of `method` (LinearTFT / LinearF), the `candidates`
         best refitted on their inliers `lo_rounds` times, the best one returned.  scene (Ns, 6), calm (9, 3), threshold in pixels per coordinate.
         Returns dict(R_t_2 (3,4), R_t_3 (3,4), T (3,3,3) [j,k,i], mask (Ns,) uint8, inliers, hypothesis, refits, candidates, status): CUDA tensors in
@@ -1067,8 +1191,9 @@ class Context:
         first_round the first round's length, and n_hyp_used joins the dict; the result is that of this call with n_hyp = n_hyp_used.
         order= (Ns,) int32, the matches best first, or quality= (Ns,) float, higher is better, with growth: the guided sampler of robust_pose_scenes for
         this one scene (the S = 1 call with the offsets [0, Ns]); n_hyp_used joins the dict only with a confidence.  Without them nothing changes.
-        polish_loss, polish_scale, polish_all: as robust_pose_scenes; weight_polished (Ns,) joins the dict."""
-        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold)
+        polish_loss, polish_scale, polish_all: as robust_pose_scenes; weight_polished (Ns,) joins the dict.  polish_cov=True: cov_polished (12,12) and
+        sigma0_polished, as robust_pose_scenes."""
+        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold, polish, polish_cov)
         if method not in ROBUST_METHODS:
             raise ValueError("robust_pose draws its hypotheses with LinearTFTPoseEstimation or LinearFPoseEstimation, not %r" % (method,))
         if refine is not None and refine not in POSE_METHODS:
@@ -1140,6 +1265,8 @@ class Context:
             if host:
                 out["iter_polished"] = int(out["iter_polished"]); out["status_polished"] = int(out["status_polished"])
                 out["repr_err_polished"] = float(out["repr_err_polished"])
+                if how[3]:
+                    out["sigma0_polished"] = float(out["sigma0_polished"])
         return out
 
     @staticmethod
@@ -1189,7 +1316,7 @@ class Context:
 
     def robust_pose_scenes(self, method, scenes, offsets, calm, n_hyp, threshold, seed=0, n_sample=None, candidates=16, lo_rounds=2, ns_max=None,
                            polish=False, refine=None, confidence=None, first_round=256, order=None, quality=None, growth=200000, polish_loss=None,
-                           polish_scale=None, polish_all=False):
+                           polish_scale=None, polish_all=False, polish_cov=False):
         """robust_pose for S scenes in one call (tff_robust_pose_scenes_*): scenes (Ntot, 6) packed, offsets (S + 1,) int64 with scene s =
         scenes[offsets[s]:offsets[s + 1]] (see pack_ragged), calm (9, 3) shared or (S, 9, 3).  Scene s gets bit for bit what robust_pose returns for it alone
         with seed + s (wrapping uint64).  Returns dict(R_t_2, R_t_3 (S,3,4), T (S,3,3,3), mask (Ntot,) uint8 packed like the scenes, inliers, hypothesis,
@@ -1217,8 +1344,11 @@ class Context:
         by default `threshold`; weight_polished (Ntot,), packed like mask, joins the dict.  polish_all=True passes no mask: the polish runs over all
         matches of every scene and the loss alone keeps the wrong ones down (refused without a loss).  A scene without a pose then enters the adjustment
         with its NaN poses and leaves it with ST_NONFINITE, NaN poses and NaN weights (under the mask: ST_TOO_FEW, as before).  The three are checked before anything else and
-        otherwise ignored without polish=True."""
-        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold)
+        otherwise ignored without polish=True.
+        polish_cov=True (refused without polish=True): the polish call also returns the covariance of every polished pose (bundle_adjust_ragged(...,
+        cov=True)), as cov_polished (S,12,12) and sigma0_polished (S,): NaN for a scene without a pose or with three or fewer matches in the polish.
+        Every other key keeps its bits, and the device path still makes no synchronisation."""
+        how = self._check_polish(polish_loss, polish_scale, polish_all, threshold, polish, polish_cov)
         adaptive = None if confidence is None else _check_adaptive(confidence, first_round)
         guided = self._check_guided(scenes, order, quality, growth)
         if refine is not None and refine not in RAGGED_METHODS:

@@ -23,6 +23,7 @@
 #include "robust_layout.h"
 #include "ba_ragged_kernel.h"
 #include "ba_loss_kernel.h"
+#include "ba_cov_kernel.h"
 
 namespace {
 
@@ -82,6 +83,7 @@ struct tff_ctx {
     DevBuf guided_ends, guided_order;      // guided sampling: the pool tables (4 n_total bytes), the ranking of a _host call (4 n_total bytes)
     DevBuf ba_weight;                      // tff_bundle_adjust_loss_*_host: the staged weights
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
+    DevBuf cov_plan, cov_pack, cov_rec, cov_io;   // tff_ba_covariance_* / tff_bundle_adjust_cov_*: the plan (O(B)), the compact copies of a masked call (124 bytes x n_total), the points of a call without `reconst`, the staging of a _host call
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
     int spill_only_if_needed = 0;          // TFF_OPT_SPILL
@@ -1063,7 +1065,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 106; }
+int tff_version(void) { return 107; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1089,7 +1091,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io})
         b->release();
     delete c;
 }
@@ -1600,6 +1602,68 @@ int launch_ba_ragged(tff_ctx* c, const BaRaggedCall& q) {
     return 0;
 }
 
+// ---- covariance of the bundle adjustment (tff_ba_covariance_*, tff_bundle_adjust_cov_*; include/tftfund_cov.h, csrc/ba_cov_kernel.h) ----------------
+static_assert(tff::ba_cov_lds_bytes() <= 64 * 1024, "k_ba_cov's LDS does not grow with N");
+int launch_ba_cov_kernel(tff_ctx* c, int32_t loss, unsigned grid, const tff::BaCovArgs& a) {
+    constexpr size_t lds = tff::ba_cov_lds_bytes();
+    if (loss == TFF_LOSS_NONE) return launch(c, tff::k_ba_cov<tff::BA_LOSS_NONE>, grid, 64, lds, a);
+    return loss == TFF_LOSS_HUBER ? launch(c, tff::k_ba_cov<tff::BA_LOSS_HUBER>, grid, 64, lds, a) : launch(c, tff::k_ba_cov<tff::BA_LOSS_CAUCHY>, grid, 64, lds, a);
+}
+int check_ba_cov(const void* reconst, const void* cov, const void* sigma0, int64_t B) {
+    if (B > 0 && (!reconst || !cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs reconst, cov and sigma0");
+    return 0;
+}
+int launch_ba_cov(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2, const double* Rt3, const double* corresp, int64_t B, int32_t N,
+                  const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    return launch_ba_cov_kernel(c, loss, tff::pose_grid(B), tff::BaCovArgs{calm, (long)calm_stride, Rt2, Rt3, corresp, (long)B, N, reconst, scale, cov, sigma0, point_cov});
+}
+struct BaCovRaggedCall {                   // device pointers
+    const double* corresp; const int64_t* offsets; int64_t n_total; const uint8_t* mask; const double* calm; int64_t calm_stride;
+    const double* Rt2; const double* Rt3; const double* reconst; int64_t B; int32_t loss; double scale;
+    double* cov; double* sigma0; double* point_cov;
+};
+// The selection is that of launch_ba_ragged -- its count, scan and compact kernels on a plan of this call's own --; there are no classes (one launch, one
+// LDS size) and no largest m.  What those kernels write for an item that fails (poses, status) goes to the plan's workspace.
+int launch_ba_cov_ragged(tff_ctx* c, const BaCovRaggedCall& q) {
+    const size_t B = (size_t)q.B, nt = (size_t)q.n_total;
+    // the plan: coff (B int64) | the poses of a failed item (24 B doubles) | m (B) | status (B);  a masked call: packed (6) | points (3) | point_cov (6 doubles) | src (int32) per correspondence
+    TFF_TRY(c->cov_plan.reserve(B * (sizeof(int64_t) + 24 * sizeof(double) + 2 * sizeof(int32_t)) + 8));
+    if (q.mask) TFF_TRY(c->cov_pack.reserve(nt * ((q.point_cov ? 15 : 9) * sizeof(double) + sizeof(int32_t)) + 8));
+    tff::BaRaggedPlan p{};
+    p.offsets = (const long*)q.offsets; p.B = (long)q.B; p.n_total = (long)q.n_total; p.mask = q.mask;
+    p.bound[0] = p.bound[1] = p.bound[2] = INT32_MAX;
+    p.coff = (long*)c->cov_plan.p;
+    p.Rt2 = (double*)(p.coff + B); p.Rt3 = p.Rt2 + 12 * B;
+    p.m = (int*)(p.Rt3 + 12 * B);
+    p.status = p.m + B;
+    p.corresp = q.corresp; p.reconst0 = q.reconst;
+    double* pc_ws = nullptr;
+    if (q.mask) {
+        p.packed = (double*)c->cov_pack.p;
+        p.rec0 = p.packed + 6 * nt;
+        if (q.point_cov) pc_ws = p.rec0 + 3 * nt;
+        p.src = (int*)(p.rec0 + (q.point_cov ? 9 : 3) * nt);
+    }
+    const unsigned per_item = (unsigned)(q.B < (1L << 20) ? q.B : (1L << 20));
+    TFF_HIP(hipMemsetAsync(p.status, 0, B * sizeof(int32_t), c->stream));
+    TFF_TRY(launch(c, tff::k_ba_ragged_count, per_item, 64, 0, p));
+    if (q.mask) {
+        TFF_TRY(launch(c, tff::k_ba_ragged_scan, 1, tff::BA_RAGGED_SCAN_THREADS, 0, p));
+        TFF_TRY(launch(c, tff::k_ba_ragged_compact, per_item, tff::BA_RAGGED_TILE, 0, p));
+    }
+    TFF_TRY(launch_ba_cov_kernel(c, q.loss, tff::pose_grid(q.B), tff::ba_cov_ragged_args(p, q.calm, (long)q.calm_stride, q.Rt2, q.Rt3, q.scale, q.cov, q.sigma0, pc_ws, q.point_cov)));
+    if (q.point_cov) TFF_TRY(launch(c, tff::k_ba_cov_scatter, per_item, tff::BA_RAGGED_TILE, 0, tff::BaCovScatter{p, pc_ws, q.point_cov}));
+    return 0;
+}
+// the offsets of a ragged _host call, as tff_bundle_adjust_loss_ragged_host checks them
+int check_host_offsets(const int64_t* offsets, int64_t B) {
+    if (B < 0) return fail(TFF_E_INVALID, "negative batch size");
+    if (B > 0 && !offsets) return fail(TFF_E_INVALID, "null pointer");
+    if (B > 0 && offsets[0] < 0) return fail(TFF_E_INVALID, "offsets[0] must be >= 0");
+    for (int64_t b = 0; b < B; ++b) if (offsets[b + 1] < offsets[b]) return fail(TFF_E_INVALID, "offsets must not decrease");
+    return 0;
+}
+
 // BundleAdjustment as the reference writes it, M = 2 .. 6 views, MATLAB's own array layouts (csrc/ba_views_kernel.h)
 template <int M>
 int launch_bundle_adjust_views(tff_ctx* c, const tff::BavArgs& a) {
@@ -1794,6 +1858,166 @@ int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]) {
     if (!bounds) return fail(TFF_E_INVALID, "null pointer");
     bounds[0] = tff::BA_CLASS_BOUND_0; bounds[1] = tff::BA_CLASS_BOUND_1; bounds[2] = tff::BA_CLASS_BOUND_2;
     return 0;
+}
+
+// ---- the covariance of the adjusted poses and points (include/tftfund_cov.h) ------------------------------------------------------------------------
+int tff_ba_covariance_batch_dev(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2, const double* Rt3, const double* corresp, int64_t B,
+                                int32_t N, const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_common(corresp, calm, calm_stride, B, N));
+    TFF_TRY(check_ba_cov(reconst, cov, sigma0, B));
+    return run_batch(c, B, Rt2 && Rt3, "null pose pointer", nullptr, [&] {
+        if (N < 1) return fail(TFF_E_INVALID, "bundle adjustment needs at least one correspondence");
+        return launch_ba_cov(c, calm, calm_stride, Rt2, Rt3, corresp, B, N, reconst, loss, scale, cov, sigma0, point_cov);
+    });
+}
+int tff_ba_covariance_batch_host(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2, const double* Rt3, const double* corresp, int64_t B,
+                                 int32_t N, const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_common(corresp, calm, calm_stride, B, N));
+    TFF_TRY(check_ba_cov(reconst, cov, sigma0, B));
+    return run_batch(c, B, Rt2 && Rt3, "null pose pointer", nullptr, [&] {
+        if (N < 1) return fail(TFF_E_INVALID, "bundle adjustment needs at least one correspondence");
+        const size_t nb = (size_t)B, nn = nb * (size_t)N, ncal = (calm_stride ? nb : 1) * 27;
+        // corresp (6) | reconst (3) | point_cov (6) per correspondence, Rt2 | Rt3 | cov | sigma0 per item, calm
+        TFF_TRY(c->cov_io.reserve((15 * nn + (24 + 145) * nb + ncal) * sizeof(double)));
+        double* d_in = (double*)c->cov_io.p;
+        double* d_x = d_in + 6 * nn;
+        double* d_pc = d_x + 3 * nn;
+        double* d_r2 = d_pc + 6 * nn;
+        double* d_r3 = d_r2 + 12 * nb;
+        double* d_cov = d_r3 + 12 * nb;
+        double* d_s0 = d_cov + 144 * nb;
+        double* d_cal = d_s0 + nb;
+        TFF_HIP(hipMemcpyAsync(d_in, corresp, 6 * nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_x, reconst, 3 * nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r2, Rt2, 12 * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r3, Rt3, 12 * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_cal, calm, ncal * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_ba_cov(c, d_cal, calm_stride, d_r2, d_r3, d_in, B, N, d_x, loss, scale, d_cov, d_s0, point_cov ? d_pc : nullptr));
+        TFF_HIP(hipMemcpyAsync(cov, d_cov, 144 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipMemcpyAsync(sigma0, d_s0, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (point_cov) TFF_HIP(hipMemcpyAsync(point_cov, d_pc, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+int tff_ba_covariance_ragged_dev(tff_ctx* c, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
+                                 int64_t calm_stride, const double* Rt2, const double* Rt3, const double* reconst, int64_t B, int32_t loss, double scale,
+                                 double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2, Rt3, B, cov, sigma0));
+    if (B > 0 && n_total > 0 && !reconst) return fail(TFF_E_INVALID, "the covariance needs reconst, cov and sigma0");
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        return launch_ba_cov_ragged(c, BaCovRaggedCall{corresp, offsets, n_total, mask, calm, calm_stride, Rt2, Rt3, reconst, B, loss, scale, cov, sigma0, point_cov});
+    });
+}
+int tff_ba_covariance_ragged_host(tff_ctx* c, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm, int64_t calm_stride,
+                                  const double* Rt2, const double* Rt3, const double* reconst, int64_t B, int32_t loss, double scale, double* cov, double* sigma0,
+                                  double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_host_offsets(offsets, B));
+    const int64_t n_total = B > 0 ? offsets[B] : 0;
+    TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2, Rt3, B, cov, sigma0));
+    if (B > 0 && n_total > 0 && !reconst) return fail(TFF_E_INVALID, "the covariance needs reconst, cov and sigma0");
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        const size_t nb = (size_t)B, nt = (size_t)n_total, f = (size_t)offsets[0], cnt = nt - f, ncal = (calm_stride ? nb : 1) * 27;
+        // corresp (6) | reconst (3) | point_cov (6) per correspondence, Rt2 | Rt3 | cov | sigma0 per item, calm, offsets, mask
+        TFF_TRY(c->cov_io.reserve((15 * nt + (24 + 145) * nb + ncal) * sizeof(double) + (nb + 1) * sizeof(int64_t) + nt + 8));
+        double* d_in = (double*)c->cov_io.p;
+        double* d_x = d_in + 6 * nt;
+        double* d_pc = d_x + 3 * nt;
+        double* d_r2 = d_pc + 6 * nt;
+        double* d_r3 = d_r2 + 12 * nb;
+        double* d_cov = d_r3 + 12 * nb;
+        double* d_s0 = d_cov + 144 * nb;
+        double* d_cal = d_s0 + nb;
+        int64_t* d_off = (int64_t*)(d_cal + ncal);
+        uint8_t* d_mask = (uint8_t*)(d_off + nb + 1);
+        if (cnt) TFF_HIP(hipMemcpyAsync(d_in + 6 * f, corresp + 6 * f, cnt * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (cnt) TFF_HIP(hipMemcpyAsync(d_x + 3 * f, reconst + 3 * f, cnt * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (mask && cnt) TFF_HIP(hipMemcpyAsync(d_mask + f, mask + f, cnt, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r2, Rt2, 12 * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_r3, Rt3, 12 * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_cal, calm, ncal * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_off, offsets, (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_ba_cov_ragged(c, BaCovRaggedCall{d_in, d_off, n_total, mask ? d_mask : nullptr, d_cal, calm_stride, d_r2, d_r3, d_x, B, loss, scale, d_cov, d_s0,
+                                                        point_cov ? d_pc : nullptr}));
+        TFF_HIP(hipMemcpyAsync(cov, d_cov, 144 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipMemcpyAsync(sigma0, d_s0, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (point_cov && cnt) TFF_HIP(hipMemcpyAsync(point_cov + 6 * f, d_pc + 6 * f, cnt * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+
+// the adjustment followed by the covariance at its outputs, on one stream
+int tff_bundle_adjust_cov_batch_dev(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* corresp,
+                                    int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3, double* reconst, int32_t* iter, double* repr_err,
+                                    int32_t* status, int32_t loss, double scale, double* weight, double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_common(corresp, calm, calm_stride, B, N));
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    return run_batch(c, B, Rt2_in && Rt3_in && Rt2 && Rt3, "null pose pointer", nullptr, [&] {
+        double* rec = reconst;
+        if (!rec) {
+            TFF_TRY(c->cov_rec.reserve((size_t)B * 3 * (size_t)(N > 0 ? N : 0) * sizeof(double) + 8));
+            rec = (double*)c->cov_rec.p;
+        }
+        TFF_TRY(launch_bundle_adjust(c, tff::BaArgs{calm, (long)calm_stride, Rt2_in, Rt3_in, corresp, (long)B, N, reconst0, Rt2, Rt3, rec, iter, repr_err, status},
+                                     loss, scale, weight));
+        return launch_ba_cov(c, calm, calm_stride, Rt2, Rt3, corresp, B, N, rec, loss, scale, cov, sigma0, point_cov);
+    });
+}
+int tff_bundle_adjust_cov_ragged_dev(tff_ctx* c, const double* corresp, const int64_t* offsets, int64_t n_total, const uint8_t* mask, const double* calm,
+                                     int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3,
+                                     double* reconst, int32_t* iter, double* repr_err, int32_t* used, int32_t* status, int32_t loss, double scale, double* weight,
+                                     double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_ba_ragged(corresp, offsets, n_total, calm, calm_stride, Rt2_in, Rt3_in, B, Rt2, Rt3));
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    return run_batch(c, B, true, nullptr, &status, [&] {
+        double* rec = reconst;
+        if (!rec) {
+            TFF_TRY(c->cov_rec.reserve((size_t)n_total * 3 * sizeof(double) + 8));
+            rec = (double*)c->cov_rec.p;
+        }
+        TFF_TRY(launch_ba_ragged(c, BaRaggedCall{corresp, offsets, n_total, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, rec, iter, repr_err,
+                                                 used, status, loss, scale, weight}));
+        return launch_ba_cov_ragged(c, BaCovRaggedCall{corresp, offsets, n_total, mask, calm, calm_stride, Rt2, Rt3, rec, B, loss, scale, cov, sigma0, point_cov});
+    });
+}
+// host-pointer forms: the two host calls one after the other (each stages, runs and synchronises), the points in between kept by the caller or here
+int tff_bundle_adjust_cov_batch_host(tff_ctx* c, const double* calm, int64_t calm_stride, const double* Rt2_in, const double* Rt3_in, const double* corresp,
+                                     int64_t B, int32_t N, const double* reconst0, double* Rt2, double* Rt3, double* reconst, int32_t* iter, double* repr_err,
+                                     int32_t* status, int32_t loss, double scale, double* weight, double* cov, double* sigma0, double* point_cov) {
+    if (!c) return fail(TFF_E_INVALID, "null context");
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    std::vector<double> own;
+    double* rec = reconst;
+    if (!rec && B > 0 && N > 0) { own.resize((size_t)B * 3 * (size_t)N); rec = own.data(); }
+    TFF_TRY(tff_bundle_adjust_loss_batch_host(c, calm, calm_stride, Rt2_in, Rt3_in, corresp, B, N, reconst0, Rt2, Rt3, rec, iter, repr_err, status, loss, scale, weight));
+    return tff_ba_covariance_batch_host(c, calm, calm_stride, Rt2, Rt3, corresp, B, N, rec, loss, scale, cov, sigma0, point_cov);
+}
+int tff_bundle_adjust_cov_ragged_host(tff_ctx* c, const double* corresp, const int64_t* offsets, const uint8_t* mask, const double* calm, int64_t calm_stride,
+                                      const double* Rt2_in, const double* Rt3_in, const double* reconst0, int64_t B, double* Rt2, double* Rt3, double* reconst,
+                                      int32_t* iter, double* repr_err, int32_t* used, int32_t* status, int32_t loss, double scale, double* weight, double* cov,
+                                      double* sigma0, double* point_cov) {
+    if (!c) return fail(TFF_E_INVALID, "null context");
+    TFF_TRY(check_host_offsets(offsets, B));
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    std::vector<double> own;
+    double* rec = reconst;
+    if (!rec && B > 0 && offsets[B] > 0) { own.resize((size_t)offsets[B] * 3); rec = own.data(); }
+    TFF_TRY(tff_bundle_adjust_loss_ragged_host(c, corresp, offsets, mask, calm, calm_stride, Rt2_in, Rt3_in, reconst0, B, Rt2, Rt3, rec, iter, repr_err, used, status,
+                                               loss, scale, weight));
+    return tff_ba_covariance_ragged_host(c, corresp, offsets, mask, calm, calm_stride, Rt2, Rt3, rec, B, loss, scale, cov, sigma0, point_cov);
 }
 
 int tff_optim_f_ragged_bounds(int32_t bounds[2]) {
