@@ -337,7 +337,8 @@ int tff_bundle_adjust_ragged_class_bounds(int32_t bounds[3]);
  * Missing observations (:28-29, :165): a NaN entry is handled as the reference's code handles it -- Normalize2Ddata.m:34-37 turns
  * every point of that VIEW into NaN, :165 then skips the whole view: its camera keeps the initial angles and translation, the
  * other views are adjusted.  Without reconst0, fewer than two complete views: status TFF_ST_TOO_FEW and NaN outputs (the
- * reference stops with an error at :73-74).  Same Levenberg-Marquardt loop as tff_bundle_adjust_batch_dev. */
+ * reference stops with an error at :73-74).  Same Levenberg-Marquardt loop as tff_bundle_adjust_batch_dev.
+ * Per-POINT visibility, as the reference's header comment documents it (:4-22), is tff_bundle_adjust_tracks_batch_* of tftfund_tracks.h, included at the end. */
 int tff_bundle_adjust_views_batch_dev(tff_ctx* ctx, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in,
                                       const double* corresp, int64_t B, int32_t N, const double* reconst0, double* Rt,
                                       double* reconst, int32_t* iter, double* repr_err, int32_t* status);
@@ -533,6 +534,7 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 #endif
 #include "tftfund_adaptive.h"   /* entry points added after library version 103 */
 #include "tftfund_guided.h"     /* entry points added after library version 104 */
+#include "tftfund_tracks.h"     /* entry points added after library version 107 */
 #include "tftfund_cov.h"        /* entry points added after library version 106 (its loss codes are those of the header below) */
 #include "tftfund_loss.h"       /* entry points added after library version 105 */
 #endif

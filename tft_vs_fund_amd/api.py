@@ -148,9 +148,11 @@ def load_library(path=None):
             "tff_bundle_adjust_cov_batch_host": [V, V, I64, V, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
             "tff_bundle_adjust_cov_ragged_dev": [V, V, V, I64, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
             "tff_bundle_adjust_cov_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
+            "tff_bundle_adjust_tracks_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V],
+            "tff_bundle_adjust_tracks_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS + TRACKS_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -209,6 +211,8 @@ LOSS_IDS = {"huber": 1, "cauchy": 2}      # include/tftfund_loss.h TFF_LOSS_*; 0
 # ... and every symbol include/tftfund_cov.h declares: the entry points added after library version 106 (covariances of the bundle adjustment)
 COV_SYMBOLS = ["tff_ba_covariance_batch_dev", "tff_ba_covariance_batch_host", "tff_ba_covariance_ragged_dev", "tff_ba_covariance_ragged_host",
                "tff_bundle_adjust_cov_batch_dev", "tff_bundle_adjust_cov_batch_host", "tff_bundle_adjust_cov_ragged_dev", "tff_bundle_adjust_cov_ragged_host"]
+# ... and every symbol include/tftfund_tracks.h declares: the entry points added after library version 107 (bundle adjustment with per-point visibility)
+TRACKS_SYMBOLS = ["tff_bundle_adjust_tracks_batch_dev", "tff_bundle_adjust_tracks_batch_host"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -1072,10 +1076,23 @@ class Context:
             out.update(cov_polished=pick(ba["cov"]), sigma0_polished=pick(ba["sigma0"]))
         return out
 
-    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None):
-        """BundleAdjustment for B problems of M = 2 .. 6 views (tff_bundle_adjust_views_batch_dev): calm (3M,3) or (B,3M,3); R_t_0 (B,3M,4),
-        first camera included and free; corresp (B,N,2M), NaN = not seen (drops the whole view, as the reference's code does); reconst0 (B,3,N) or
-        None.  -> dict(R_t (B,3M,4), Reconst (B,3,N), iter, repr_err, status)."""
+    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None, missing="view"):
+        """BundleAdjustment for B problems of M = 2 .. 6 views: calm (3M,3) or (B,3M,3); R_t_0 (B,3M,4), first camera included and free; corresp
+        (B,N,2M), NaN = not seen; reconst0 (B,3,N) or None.  -> dict(R_t (B,3M,4), Reconst (B,3,N), iter, repr_err, status).
+        missing="view" (tff_bundle_adjust_views_batch_dev): a NaN drops the whole view, as the reference's code does.
+        missing="point" (tff_bundle_adjust_tracks_batch_dev, include/tftfund_tracks.h): a non-finite observation means that this point is not seen in
+        this view, as the reference's header documents; a point with fewer than two observations is dropped (its Reconst column is NaN), and `used`
+        (B,) int32, the number of points taking part, joins the dict.  An all-NaN column is inert: pad problems of different N with such columns."""
+        if missing not in ("view", "point"):
+            raise ValueError('missing must be "view" or "point"')
+        if missing == "point":                                               # (the shapes, before a device is touched)
+            cs = tuple(corresp.shape)
+            if len(cs) != 3 or cs[2] % 2 or not 2 <= cs[2] // 2 <= 6:
+                raise ValueError("corresp must be (B,N,2M) with M = 2 .. 6 views")
+            if tuple(R_t_0.shape) != (cs[0], 3 * cs[2] // 2, 4) or tuple(calm.shape) not in ((3 * cs[2] // 2, 3), (cs[0], 3 * cs[2] // 2, 3)):
+                raise ValueError("M views: corresp (B,N,2M), R_t_0 (B,3M,4), calm (3M,3) or (B,3M,3)")
+            if reconst0 is not None and tuple(reconst0.shape) != (cs[0], 3, cs[1]):
+                raise ValueError("reconst0 must be (B,3,N)")
         self._begin()
         corresp = self._t(corresp); B, N, M2 = corresp.shape
         M = M2 // 2
@@ -1094,6 +1111,13 @@ class Context:
         rec = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
         it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it)
         err = torch.empty(B, dtype=torch.float64, device=dev)
+        if missing == "point":
+            used = torch.zeros_like(it)
+            _check(self.lib, self.lib.tff_bundle_adjust_tracks_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N,
+                                                                         self._p(x0), self._p(out), self._p(rec), self._p(it), self._p(err), self._p(used),
+                                                                         self._p(st)),
+                   "tff_bundle_adjust_tracks_batch_dev")
+            return dict(R_t=out.transpose(1, 2), Reconst=rec.transpose(1, 2), iter=it, repr_err=err, used=used, status=st)
         _check(self.lib, self.lib.tff_bundle_adjust_views_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N,
                                                                     self._p(x0), self._p(out), self._p(rec), self._p(it), self._p(err), self._p(st)),
                "tff_bundle_adjust_views_batch_dev")
@@ -1612,11 +1636,16 @@ def PiColPoseEstimation(Corresp, CalM):
     return _single("PiColPoseEstimation", Corresp, CalM)
 
 
-def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None):
+def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None, missing="view"):
     """Drop-in for Optimization/BundleAdjustment.m, M = 2 .. 6 views: CalM 3Mx3, R_t_0 3Mx4, Corresp 2MxN (NaN = not seen), Reconst0 3xN or None
     -> R_t (3Mx4, first camera [I|0], |t2| = 1), Reconst (3xN), iter, repr_err.  The initial triangulation (:59-77), the change of coordinates to
     camera 1 (:80-86) and the `isnan` branch (:165 -- it drops a whole VIEW, see csrc/ba_views_kernel.h) run on the device as the reference orders them.
-    Raises ValueError where the reference stops with an error (fewer than two complete views to triangulate from, :73-74)."""
+    Raises ValueError where the reference stops with an error (fewer than two complete views to triangulate from, :73-74).
+    missing="point": what the reference's header documents instead (:4-22; include/tftfund_tracks.h) -- a NaN means that this point is not seen in this
+    view; a point seen in fewer than two views is dropped and its column of Reconst is NaN.  Raises ValueError when no point is seen in two views or a
+    view's normalisation is not finite (a view with a single observation)."""
+    if missing not in ("view", "point"):
+        raise ValueError('missing must be "view" or "point"')
     CalM = np.asarray(CalM, dtype=np.float64); R_t_0 = np.asarray(R_t_0, dtype=np.float64); Corresp = np.asarray(Corresp, dtype=np.float64)
     if Corresp.ndim != 2 or Corresp.shape[0] % 2 or not 2 <= Corresp.shape[0] // 2 <= 6:
         raise ValueError("Corresp must be 2M x N with M = 2 .. 6 views")
@@ -1624,6 +1653,15 @@ def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None):
     if R_t_0.shape != (3 * M, 4) or CalM.shape != (3 * M, 3):
         raise ValueError("%d views: R_t_0 must be %dx4 and CalM %dx3" % (M, 3 * M, 3 * M))
     X0 = None if Reconst0 is None else np.asarray(Reconst0, dtype=np.float64)[None]
+    if missing == "point":
+        if X0 is not None and X0.shape != (1, 3, Corresp.shape[1]):
+            raise ValueError("Reconst0 must be 3 x N")
+        out = default_context().bundle_adjust_views(CalM, R_t_0[None], np.ascontiguousarray(Corresp.T)[None], X0, missing="point")
+        if int(out["status"][0]) == 1:
+            raise ValueError("no point is seen in two views")
+        if int(out["used"][0]) > 0 and bool(torch.isnan(out["R_t"][0]).all()):
+            raise ValueError("a view's normalisation is not finite (Normalize2Ddata.m:35-37: a single observation, or coincident ones)")
+        return out["R_t"][0].cpu().numpy(), out["Reconst"][0].cpu().numpy(), int(out["iter"][0]), float(out["repr_err"][0])
     out = default_context().bundle_adjust_views(CalM, R_t_0[None], np.ascontiguousarray(Corresp.T)[None], X0)
     if int(out["status"][0]) == 1:
         raise ValueError("fewer than two complete views: triangulation3D returns nothing (triangulation3D.m:36-38) and BundleAdjustment.m:73-74 stops")

@@ -24,6 +24,7 @@
 #include "ba_ragged_kernel.h"
 #include "ba_loss_kernel.h"
 #include "ba_cov_kernel.h"
+#include "ba_tracks_kernel.h"
 
 namespace {
 
@@ -84,6 +85,7 @@ struct tff_ctx {
     DevBuf ba_weight;                      // tff_bundle_adjust_loss_*_host: the staged weights
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     DevBuf cov_plan, cov_pack, cov_rec, cov_io;   // tff_ba_covariance_* / tff_bundle_adjust_cov_*: the plan (O(B)), the compact copies of a masked call (124 bytes x n_total), the points of a call without `reconst`, the staging of a _host call
+    DevBuf tracks_used;                    // tff_bundle_adjust_tracks_batch_host: the staged `used` (4 B bytes)
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
     int spill_only_if_needed = 0;          // TFF_OPT_SPILL
@@ -1065,7 +1067,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 107; }
+int tff_version(void) { return 108; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1091,7 +1093,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io, &c->tracks_used})
         b->release();
     delete c;
 }
@@ -1678,6 +1680,20 @@ int launch_bundle_adjust_views(tff_ctx* c, int32_t M, const tff::BavArgs& a) {
         default: return launch_bundle_adjust_views<6>(c, a);
     }
 }
+// ... over tracks: a non-finite observation is a point not seen in that view (csrc/ba_tracks_kernel.h, include/tftfund_tracks.h)
+template <int M>
+int launch_bundle_adjust_tracks(tff_ctx* c, const tff::BatArgs& a) {
+    return launch(c, tff::k_bundle_adjust_tracks<M>, tff::pose_grid(a.v.B), 64, tff::bav_lds_bytes<M>(a.v.N), a);
+}
+int launch_bundle_adjust_tracks(tff_ctx* c, int32_t M, const tff::BatArgs& a) {
+    switch (M) {
+        case 2: return launch_bundle_adjust_tracks<2>(c, a);
+        case 3: return launch_bundle_adjust_tracks<3>(c, a);
+        case 4: return launch_bundle_adjust_tracks<4>(c, a);
+        case 5: return launch_bundle_adjust_tracks<5>(c, a);
+        default: return launch_bundle_adjust_tracks<6>(c, a);
+    }
+}
 int check_views(int32_t M, const void* calm, int64_t calm_stride, const void* Rt_in, const void* corresp, int64_t B, int32_t N, const void* Rt) {
     if (M < tff::BAV_MIN_VIEWS || M > tff::BAV_MAX_VIEWS) return fail(TFF_E_INVALID, "bundle adjustment takes 2 .. 6 views");
     if (B < 0 || N < 0) return fail(TFF_E_INVALID, "negative batch or correspondence count");
@@ -2051,6 +2067,39 @@ int tff_bundle_adjust_views_batch_host(tff_ctx* c, int32_t M, const double* calm
         TFF_TRY(launch_bundle_adjust_views(c, M, tff::BavArgs{s.calm, (long)calm_stride, s.poses_in, s.corresp, (long)B, N, s.reconst0, s.poses_out, s.reconst,
                                                               s.iter, s.repr_err, s.status}));
         TFF_HIP(hipMemcpyAsync(Rt, s.poses_out, npose, hipMemcpyDeviceToHost, c->stream));
+        return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
+    });
+}
+
+// BundleAdjustment as the reference documents it: per-point visibility (launch_bundle_adjust_tracks above; include/tftfund_tracks.h)
+int tff_bundle_adjust_tracks_batch_dev(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                       int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                       int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        return launch_bundle_adjust_tracks(c, M, tff::BatArgs{tff::BavArgs{calm, (long)calm_stride, Rt_in, corresp, (long)B, N, reconst0, Rt, reconst, iter, repr_err,
+                                                                           status}, used});
+    });
+}
+int tff_bundle_adjust_tracks_batch_host(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                        int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                        int32_t* used, int32_t* status) {
+    TFF_ENTER(c);
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        const size_t nin = (size_t)B * 2 * M * (size_t)N * sizeof(double), npt = (size_t)B * 3 * (size_t)N * sizeof(double);
+        const size_t ncal = (calm_stride ? (size_t)B : 1) * 9 * M * sizeof(double), npose = (size_t)B * 12 * M * sizeof(double);
+        BaStaging s;
+        TFF_TRY(ba_stage_in(c, (size_t)B, nin, npt, npose, ncal, corresp, reconst0, &s));
+        TFF_TRY(c->tracks_used.reserve((size_t)B * sizeof(int32_t)));
+        int32_t* d_used = (int32_t*)c->tracks_used.p;
+        TFF_HIP(hipMemcpyAsync(s.poses_in, Rt_in, npose, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(s.calm, calm, ncal, hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_bundle_adjust_tracks(c, M, tff::BatArgs{tff::BavArgs{s.calm, (long)calm_stride, s.poses_in, s.corresp, (long)B, N, s.reconst0, s.poses_out,
+                                                                            s.reconst, s.iter, s.repr_err, s.status}, d_used}));
+        TFF_HIP(hipMemcpyAsync(Rt, s.poses_out, npose, hipMemcpyDeviceToHost, c->stream));
+        if (used) TFF_HIP(hipMemcpyAsync(used, d_used, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
     });
 }
