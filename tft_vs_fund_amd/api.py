@@ -150,9 +150,11 @@ def load_library(path=None):
             "tff_bundle_adjust_cov_ragged_host": [V, V, V, V, V, I64, V, V, V, I64, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
             "tff_bundle_adjust_tracks_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V],
             "tff_bundle_adjust_tracks_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V],
+            "tff_bundle_adjust_tracks_loss_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_bundle_adjust_tracks_loss_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS + TRACKS_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS + TRACKS_SYMBOLS + TRACKS_LOSS_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -213,6 +215,8 @@ COV_SYMBOLS = ["tff_ba_covariance_batch_dev", "tff_ba_covariance_batch_host", "t
                "tff_bundle_adjust_cov_batch_dev", "tff_bundle_adjust_cov_batch_host", "tff_bundle_adjust_cov_ragged_dev", "tff_bundle_adjust_cov_ragged_host"]
 # ... and every symbol include/tftfund_tracks.h declares: the entry points added after library version 107 (bundle adjustment with per-point visibility)
 TRACKS_SYMBOLS = ["tff_bundle_adjust_tracks_batch_dev", "tff_bundle_adjust_tracks_batch_host"]
+# ... and every symbol include/tftfund_tracks_loss.h declares: the entry points added after library version 108 (robust losses over tracks)
+TRACKS_LOSS_SYMBOLS = ["tff_bundle_adjust_tracks_loss_batch_dev", "tff_bundle_adjust_tracks_loss_batch_host"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -1076,15 +1080,19 @@ class Context:
             out.update(cov_polished=pick(ba["cov"]), sigma0_polished=pick(ba["sigma0"]))
         return out
 
-    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None, missing="view"):
+    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None, missing="view", loss=None, scale=None):
         """BundleAdjustment for B problems of M = 2 .. 6 views: calm (3M,3) or (B,3M,3); R_t_0 (B,3M,4), first camera included and free; corresp
         (B,N,2M), NaN = not seen; reconst0 (B,3,N) or None.  -> dict(R_t (B,3M,4), Reconst (B,3,N), iter, repr_err, status).
         missing="view" (tff_bundle_adjust_views_batch_dev): a NaN drops the whole view, as the reference's code does.
         missing="point" (tff_bundle_adjust_tracks_batch_dev, include/tftfund_tracks.h): a non-finite observation means that this point is not seen in
         this view, as the reference's header documents; a point with fewer than two observations is dropped (its Reconst column is NaN), and `used`
-        (B,) int32, the number of points taking part, joins the dict.  An all-NaN column is inert: pad problems of different N with such columns."""
+        (B,) int32, the number of points taking part, joins the dict.  An all-NaN column is inert: pad problems of different N with such columns.
+        loss="huber" | "cauchy" with scale (pixels), missing="point" only (tff_bundle_adjust_tracks_loss_batch_dev, include/tftfund_tracks_loss.h): the
+        loss is taken per OBSERVATION, repr_err is sqrt(sum rho) in pixels, and `weight` (B,N,M) joins the dict: rho' of every observation at the final
+        parameters, NaN where there is no observation, over a dropped point and over an item whose status is not 0."""
         if missing not in ("view", "point"):
             raise ValueError('missing must be "view" or "point"')
+        _check_tracks_loss(missing, loss, scale)                             # (before a device is touched)
         if missing == "point":                                               # (the shapes, before a device is touched)
             cs = tuple(corresp.shape)
             if len(cs) != 3 or cs[2] % 2 or not 2 <= cs[2] // 2 <= 6:
@@ -1111,6 +1119,14 @@ class Context:
         rec = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
         it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it)
         err = torch.empty(B, dtype=torch.float64, device=dev)
+        if missing == "point" and loss is not None:
+            used = torch.zeros_like(it)
+            weight = torch.empty((B, N, M), dtype=torch.float64, device=dev)
+            _check(self.lib, self.lib.tff_bundle_adjust_tracks_loss_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N,
+                                                                              self._p(x0), self._p(out), self._p(rec), self._p(it), self._p(err), self._p(used),
+                                                                              self._p(st), LOSS_IDS[loss], float(scale), self._p(weight)),
+                   "tff_bundle_adjust_tracks_loss_batch_dev")
+            return dict(R_t=out.transpose(1, 2), Reconst=rec.transpose(1, 2), iter=it, repr_err=err, used=used, status=st, weight=weight)
         if missing == "point":
             used = torch.zeros_like(it)
             _check(self.lib, self.lib.tff_bundle_adjust_tracks_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N,
@@ -1636,16 +1652,31 @@ def PiColPoseEstimation(Corresp, CalM):
     return _single("PiColPoseEstimation", Corresp, CalM)
 
 
-def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None, missing="view"):
+def _check_tracks_loss(missing, loss, scale):
+    """loss= / scale= of bundle_adjust_views and BundleAdjustment: ValueError before a device is touched"""
+    if loss is None:
+        return
+    if not isinstance(loss, str) or loss not in LOSS_IDS:
+        raise ValueError('loss must be None, "huber" or "cauchy"')
+    if missing != "point":
+        raise ValueError('a loss needs missing="point": the whole-view call has none')
+    if scale is None or isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (0.0 < float(scale) < float("inf")):
+        raise ValueError("a loss needs a positive finite scale (pixels)")
+
+
+def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None, missing="view", loss=None, scale=None):
     """Drop-in for Optimization/BundleAdjustment.m, M = 2 .. 6 views: CalM 3Mx3, R_t_0 3Mx4, Corresp 2MxN (NaN = not seen), Reconst0 3xN or None
     -> R_t (3Mx4, first camera [I|0], |t2| = 1), Reconst (3xN), iter, repr_err.  The initial triangulation (:59-77), the change of coordinates to
     camera 1 (:80-86) and the `isnan` branch (:165 -- it drops a whole VIEW, see csrc/ba_views_kernel.h) run on the device as the reference orders them.
     Raises ValueError where the reference stops with an error (fewer than two complete views to triangulate from, :73-74).
     missing="point": what the reference's header documents instead (:4-22; include/tftfund_tracks.h) -- a NaN means that this point is not seen in this
     view; a point seen in fewer than two views is dropped and its column of Reconst is NaN.  Raises ValueError when no point is seen in two views or a
-    view's normalisation is not finite (a view with a single observation)."""
+    view's normalisation is not finite (a view with a single observation).
+    loss="huber" | "cauchy", scale in pixels (missing="point" only; include/tftfund_tracks_loss.h): a robust loss per observation; repr_err is then
+    sqrt(sum rho) in pixels."""
     if missing not in ("view", "point"):
         raise ValueError('missing must be "view" or "point"')
+    _check_tracks_loss(missing, loss, scale)
     CalM = np.asarray(CalM, dtype=np.float64); R_t_0 = np.asarray(R_t_0, dtype=np.float64); Corresp = np.asarray(Corresp, dtype=np.float64)
     if Corresp.ndim != 2 or Corresp.shape[0] % 2 or not 2 <= Corresp.shape[0] // 2 <= 6:
         raise ValueError("Corresp must be 2M x N with M = 2 .. 6 views")
@@ -1656,7 +1687,7 @@ def BundleAdjustment(CalM, R_t_0, Corresp, Reconst0=None, missing="view"):
     if missing == "point":
         if X0 is not None and X0.shape != (1, 3, Corresp.shape[1]):
             raise ValueError("Reconst0 must be 3 x N")
-        out = default_context().bundle_adjust_views(CalM, R_t_0[None], np.ascontiguousarray(Corresp.T)[None], X0, missing="point")
+        out = default_context().bundle_adjust_views(CalM, R_t_0[None], np.ascontiguousarray(Corresp.T)[None], X0, missing="point", loss=loss, scale=scale)
         if int(out["status"][0]) == 1:
             raise ValueError("no point is seen in two views")
         if int(out["used"][0]) > 0 and bool(torch.isnan(out["R_t"][0]).all()):

@@ -25,6 +25,7 @@
 #include "ba_loss_kernel.h"
 #include "ba_cov_kernel.h"
 #include "ba_tracks_kernel.h"
+#include "ba_tracks_loss_kernel.h"
 
 namespace {
 
@@ -86,6 +87,7 @@ struct tff_ctx {
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     DevBuf cov_plan, cov_pack, cov_rec, cov_io;   // tff_ba_covariance_* / tff_bundle_adjust_cov_*: the plan (O(B)), the compact copies of a masked call (124 bytes x n_total), the points of a call without `reconst`, the staging of a _host call
     DevBuf tracks_used;                    // tff_bundle_adjust_tracks_batch_host: the staged `used` (4 B bytes)
+    DevBuf tracks_weight, tracks_status;   // tff_bundle_adjust_tracks_loss_batch_*: the staged weights of a _host call (8 B N M bytes); the statuses of a TFF_LOSS_NONE call with weights and no status output (4 B bytes)
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
     int spill_only_if_needed = 0;          // TFF_OPT_SPILL
@@ -1067,7 +1069,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 108; }
+int tff_version(void) { return 109; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1093,7 +1095,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io, &c->tracks_used})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io, &c->tracks_used, &c->tracks_weight, &c->tracks_status})
         b->release();
     delete c;
 }
@@ -1694,6 +1696,35 @@ int launch_bundle_adjust_tracks(tff_ctx* c, int32_t M, const tff::BatArgs& a) {
         default: return launch_bundle_adjust_tracks<6>(c, a);
     }
 }
+// ... with a robust loss per observation (csrc/ba_tracks_loss_kernel.h, include/tftfund_tracks_loss.h).  TFF_LOSS_NONE is the plain call, the same kernel
+// instance, and a small kernel of its own for the weights.
+template <int M>
+int launch_bundle_adjust_tracks_loss(tff_ctx* c, int32_t loss, const tff::BatLossArgs& a) {
+    const unsigned grid = tff::pose_grid(a.t.v.B);
+    const size_t lds = tff::bav_lds_bytes<M>(a.t.v.N);
+    return loss == TFF_LOSS_HUBER ? launch(c, tff::k_bundle_adjust_tracks_loss<M, tff::BA_LOSS_HUBER>, grid, 64, lds, a)
+                                  : launch(c, tff::k_bundle_adjust_tracks_loss<M, tff::BA_LOSS_CAUCHY>, grid, 64, lds, a);
+}
+int launch_bundle_adjust_tracks_loss(tff_ctx* c, int32_t M, tff::BatArgs a, int32_t loss, double scale, double* weight) {
+    if (loss == TFF_LOSS_NONE) {
+        if (weight && !a.v.status) {                                         // the weights of an item that failed are NaN: its status is needed
+            TFF_TRY(c->tracks_status.reserve((size_t)a.v.B * sizeof(int32_t) + 8));
+            a.v.status = (int*)c->tracks_status.p;
+        }
+        TFF_TRY(launch_bundle_adjust_tracks(c, M, a));
+        if (!weight) return 0;
+        const long blocks = (a.v.B * (long)a.v.N + 255) / 256;
+        return launch(c, tff::k_bat_weight_ones, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, tff::BatOnesArgs{weight, a.v.corresp, a.v.status, a.v.B, a.v.N, M});
+    }
+    const tff::BatLossArgs la{a, scale, weight};
+    switch (M) {
+        case 2: return launch_bundle_adjust_tracks_loss<2>(c, loss, la);
+        case 3: return launch_bundle_adjust_tracks_loss<3>(c, loss, la);
+        case 4: return launch_bundle_adjust_tracks_loss<4>(c, loss, la);
+        case 5: return launch_bundle_adjust_tracks_loss<5>(c, loss, la);
+        default: return launch_bundle_adjust_tracks_loss<6>(c, loss, la);
+    }
+}
 int check_views(int32_t M, const void* calm, int64_t calm_stride, const void* Rt_in, const void* corresp, int64_t B, int32_t N, const void* Rt) {
     if (M < tff::BAV_MIN_VIEWS || M > tff::BAV_MAX_VIEWS) return fail(TFF_E_INVALID, "bundle adjustment takes 2 .. 6 views");
     if (B < 0 || N < 0) return fail(TFF_E_INVALID, "negative batch or correspondence count");
@@ -2100,6 +2131,45 @@ int tff_bundle_adjust_tracks_batch_host(tff_ctx* c, int32_t M, const double* cal
                                                                             s.reconst, s.iter, s.repr_err, s.status}, d_used}));
         TFF_HIP(hipMemcpyAsync(Rt, s.poses_out, npose, hipMemcpyDeviceToHost, c->stream));
         if (used) TFF_HIP(hipMemcpyAsync(used, d_used, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
+    });
+}
+
+// ... with a robust loss per observation and the weights (launch_bundle_adjust_tracks_loss above; include/tftfund_tracks_loss.h)
+int tff_bundle_adjust_tracks_loss_batch_dev(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                            int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                            int32_t* used, int32_t* status, int32_t loss, double scale, double* weight) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        return launch_bundle_adjust_tracks_loss(c, M, tff::BatArgs{tff::BavArgs{calm, (long)calm_stride, Rt_in, corresp, (long)B, N, reconst0, Rt, reconst, iter,
+                                                                                repr_err, status}, used}, loss, scale, weight);
+    });
+}
+int tff_bundle_adjust_tracks_loss_batch_host(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                             int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                             int32_t* used, int32_t* status, int32_t loss, double scale, double* weight) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        const size_t nin = (size_t)B * 2 * M * (size_t)N * sizeof(double), npt = (size_t)B * 3 * (size_t)N * sizeof(double);
+        const size_t ncal = (calm_stride ? (size_t)B : 1) * 9 * M * sizeof(double), npose = (size_t)B * 12 * M * sizeof(double);
+        const size_t nw = (size_t)B * (size_t)N * M * sizeof(double);
+        BaStaging s;
+        TFF_TRY(ba_stage_in(c, (size_t)B, nin, npt, npose, ncal, corresp, reconst0, &s));
+        TFF_TRY(c->tracks_used.reserve((size_t)B * sizeof(int32_t)));
+        int32_t* d_used = (int32_t*)c->tracks_used.p;
+        if (weight) TFF_TRY(c->tracks_weight.reserve(nw));
+        double* d_w = weight ? (double*)c->tracks_weight.p : nullptr;
+        TFF_HIP(hipMemcpyAsync(s.poses_in, Rt_in, npose, hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(s.calm, calm, ncal, hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_bundle_adjust_tracks_loss(c, M, tff::BatArgs{tff::BavArgs{s.calm, (long)calm_stride, s.poses_in, s.corresp, (long)B, N, s.reconst0, s.poses_out,
+                                                                                 s.reconst, s.iter, s.repr_err, s.status}, d_used}, loss, scale, d_w));
+        TFF_HIP(hipMemcpyAsync(Rt, s.poses_out, npose, hipMemcpyDeviceToHost, c->stream));
+        if (used) TFF_HIP(hipMemcpyAsync(used, d_used, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (weight) TFF_HIP(hipMemcpyAsync(weight, d_w, nw, hipMemcpyDeviceToHost, c->stream));
         return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
     });
 }
