@@ -536,6 +536,7 @@ int tff_optim_f_ragged_bounds(int32_t bounds[2]);
 #include "tftfund_guided.h"     /* entry points added after library version 104 */
 #include "tftfund_tracks.h"     /* entry points added after library version 107 */
 #include "tftfund_tracks_loss.h" /* entry points added after library version 108 (its loss codes are those of the last header below) */
+#include "tftfund_tracks_cov.h" /* entry points added after library version 109 (its loss codes are those of the last header below) */
 #include "tftfund_cov.h"        /* entry points added after library version 106 (its loss codes are those of the header below) */
 #include "tftfund_loss.h"       /* entry points added after library version 105 */
 #endif

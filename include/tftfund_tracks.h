@@ -22,7 +22,7 @@
  * Every output pointer except Rt may be NULL.  TFF_E_INVALID, before any work: what tff_bundle_adjust_views_batch_* refuse (a null context, M outside 2 .. 6,
  * negative B or N, N = 0 with B > 0, a null calm, Rt_in, corresp or Rt, a calm_stride other than 0 or 9 M).  LDS: that of the whole-view call, 48 N bytes plus
  * a fixed part; nothing is kept per point beyond that (the visibility is read from the observations).  Workspace of the _host form: its staging, 4 B bytes more.
- * Losses for M views: tftfund_tracks_loss.h.  Not here: covariances for M views, more than six views, a loss in the polish of tff_robust_pose_scenes_* over
+ * Losses for M views: tftfund_tracks_loss.h; covariances for M views: tftfund_tracks_cov.h.  Not here: more than six views, a loss in the polish of tff_robust_pose_scenes_* over
  * tracks, merging of tracks. */
 #ifndef TFTFUND_TRACKS_H
 #define TFTFUND_TRACKS_H

@@ -33,7 +33,7 @@
  * columns of reconst or of the other rows of weight.  Problems of different N therefore go into one call padded with NaN columns; that is the ragged form
  * of this call.  An item's outputs do not depend on the other items of the batch.  Every output pointer except Rt may be NULL.  LDS: that of the plain
  * tracks call; the loss keeps nothing per point.  Workspace of the _host form beyond that of tff_bundle_adjust_tracks_batch_host: 8 B N M bytes for the
- * staged weights.  Not here: covariances for M views, more than six views, a loss in the polish of tff_robust_pose_scenes_* over tracks. */
+ * staged weights.  Covariances for M views: tftfund_tracks_cov.h.  Not here: more than six views, a loss in the polish of tff_robust_pose_scenes_* over tracks. */
 #ifndef TFTFUND_TRACKS_LOSS_H
 #define TFTFUND_TRACKS_LOSS_H
 #include "tftfund.h"

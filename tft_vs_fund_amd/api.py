@@ -152,9 +152,13 @@ def load_library(path=None):
             "tff_bundle_adjust_tracks_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V],
             "tff_bundle_adjust_tracks_loss_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
             "tff_bundle_adjust_tracks_loss_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V],
+            "tff_ba_tracks_covariance_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, I32, F64, V, V, V],
+            "tff_ba_tracks_covariance_batch_host": [V, I32, V, I64, V, V, I64, I32, V, I32, F64, V, V, V],
+            "tff_bundle_adjust_tracks_cov_batch_dev": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
+            "tff_bundle_adjust_tracks_cov_batch_host": [V, I32, V, I64, V, V, I64, I32, V, V, V, V, V, V, V, I32, F64, V, V, V, V],
         }
         for name, sig in protos.items():
-            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS + TRACKS_SYMBOLS + TRACKS_LOSS_SYMBOLS and not hasattr(lib, name):
+            if path is not None and name in ADAPTIVE_SYMBOLS + GUIDED_SYMBOLS + LOSS_SYMBOLS + COV_SYMBOLS + TRACKS_SYMBOLS + TRACKS_LOSS_SYMBOLS + TRACKS_COV_SYMBOLS and not hasattr(lib, name):
                 continue                                                     # (an older build, loaded by its path next to this one for a comparison)
             fn = getattr(lib, name)
             fn.argtypes = sig
@@ -217,6 +221,9 @@ COV_SYMBOLS = ["tff_ba_covariance_batch_dev", "tff_ba_covariance_batch_host", "t
 TRACKS_SYMBOLS = ["tff_bundle_adjust_tracks_batch_dev", "tff_bundle_adjust_tracks_batch_host"]
 # ... and every symbol include/tftfund_tracks_loss.h declares: the entry points added after library version 108 (robust losses over tracks)
 TRACKS_LOSS_SYMBOLS = ["tff_bundle_adjust_tracks_loss_batch_dev", "tff_bundle_adjust_tracks_loss_batch_host"]
+# ... and every symbol include/tftfund_tracks_cov.h declares: the entry points added after library version 109 (covariances over tracks)
+TRACKS_COV_SYMBOLS = ["tff_ba_tracks_covariance_batch_dev", "tff_ba_tracks_covariance_batch_host", "tff_bundle_adjust_tracks_cov_batch_dev",
+                      "tff_bundle_adjust_tracks_cov_batch_host"]
 
 # method ids of the multi-GPU entry points (include/tftfund.h TFF_METHOD_*: the order of experiments.m:51-59)
 METHOD_IDS = {"LinearTFTPoseEstimation": 0, "ResslTFTPoseEstimation": 1, "NordbergTFTPoseEstimation": 2, "FaugPapaTFTPoseEstimation": 3,
@@ -440,6 +447,32 @@ def euler_cov_to_rotvec(R_t_2, R_t_3, cov):
     for b in range(cv.shape[0]):
         T = np.eye(12)
         for j, R in enumerate((r2[b][:, :3], r3[b][:, :3])):
+            a = -np.arctan2(R[1, 2], R[2, 2]); bb = -np.arctan2(-R[0, 2], np.hypot(R[1, 2], R[2, 2]))
+            ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(bb), np.sin(bb)
+            Rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]]); Ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]])
+            T[3 * j:3 * j + 3, 3 * j:3 * j + 3] = np.stack([np.array([1.0, 0, 0]), Rx[:, 1], (Rx @ Ry)[:, 2]], axis=1)
+        out[b] = T @ cv[b] @ T.T
+    return out[0] if single else out
+
+
+def euler_cov_to_rotvec_views(R_t, cov):
+    """euler_cov_to_rotvec for the M - 1 cameras of a bundle adjustment over tracks (bundle_adjust_views(..., missing="point", cov=True),
+    ba_tracks_covariance: parameters angles of cameras 2..M, then their translations): the same first-order map to LEFT-PERTURBATION ROTATION-VECTOR
+    coordinates, omega_j = e_x da + Rx e_y db + Rx Ry e_z dc per camera; the translations pass through.  Host helper, numpy: R_t (3M,4) or (B,3M,4),
+    cov (P,P) or (B,P,P) with P = 6 (M - 1) -> the same shape."""
+    to_np = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    rt, cv = to_np(R_t), to_np(cov)
+    single = cv.ndim == 2
+    if single:
+        rt, cv = rt[None], cv[None]
+    if rt.ndim != 3 or rt.shape[2] != 4 or rt.shape[1] % 3 or not 2 <= rt.shape[1] // 3 <= 6 or cv.shape != (rt.shape[0],) + (6 * (rt.shape[1] // 3 - 1),) * 2:
+        raise ValueError("R_t must be (B, 3M, 4) with M = 2 .. 6 and cov (B, 6 (M - 1), 6 (M - 1))")
+    C = rt.shape[1] // 3 - 1
+    out = np.empty_like(cv)
+    for b in range(cv.shape[0]):
+        T = np.eye(6 * C)
+        for j in range(C):
+            R = rt[b][3 * j + 3:3 * j + 6, :3]
             a = -np.arctan2(R[1, 2], R[2, 2]); bb = -np.arctan2(-R[0, 2], np.hypot(R[1, 2], R[2, 2]))
             ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(bb), np.sin(bb)
             Rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]]); Ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]])
@@ -1080,7 +1113,7 @@ class Context:
             out.update(cov_polished=pick(ba["cov"]), sigma0_polished=pick(ba["sigma0"]))
         return out
 
-    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None, missing="view", loss=None, scale=None):
+    def bundle_adjust_views(self, calm, R_t_0, corresp, reconst0=None, missing="view", loss=None, scale=None, cov=False, point_cov=False):
         """BundleAdjustment for B problems of M = 2 .. 6 views: calm (3M,3) or (B,3M,3); R_t_0 (B,3M,4), first camera included and free; corresp
         (B,N,2M), NaN = not seen; reconst0 (B,3,N) or None.  -> dict(R_t (B,3M,4), Reconst (B,3,N), iter, repr_err, status).
         missing="view" (tff_bundle_adjust_views_batch_dev): a NaN drops the whole view, as the reference's code does.
@@ -1089,10 +1122,16 @@ class Context:
         (B,) int32, the number of points taking part, joins the dict.  An all-NaN column is inert: pad problems of different N with such columns.
         loss="huber" | "cauchy" with scale (pixels), missing="point" only (tff_bundle_adjust_tracks_loss_batch_dev, include/tftfund_tracks_loss.h): the
         loss is taken per OBSERVATION, repr_err is sqrt(sum rho) in pixels, and `weight` (B,N,M) joins the dict: rho' of every observation at the final
-        parameters, NaN where there is no observation, over a dropped point and over an item whose status is not 0."""
+        parameters, NaN where there is no observation, over a dropped point and over an item whose status is not 0.
+        cov=True, missing="point" only (tff_bundle_adjust_tracks_cov_batch_dev, include/tftfund_tracks_cov.h): cov (B,P,P), P = 6 (M - 1), the covariance
+        of (angles of cameras 2..M, their translations) in the gauge |t2| = 1, and sigma0 (B,) join the dict; point_cov=True adds them and point_cov
+        (B,N,6), every point's 3x3 block packed xx xy xz yy yz zz, NaN over a dropped point.  They are what ba_tracks_covariance gives on this call's
+        outputs, and every other output keeps its bits."""
         if missing not in ("view", "point"):
             raise ValueError('missing must be "view" or "point"')
         _check_tracks_loss(missing, loss, scale)                             # (before a device is touched)
+        if (cov or point_cov) and missing != "point":
+            raise ValueError('a covariance needs missing="point": the whole-view call has none')
         if missing == "point":                                               # (the shapes, before a device is touched)
             cs = tuple(corresp.shape)
             if len(cs) != 3 or cs[2] % 2 or not 2 <= cs[2] // 2 <= 6:
@@ -1119,6 +1158,22 @@ class Context:
         rec = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
         it = torch.zeros(B, dtype=torch.int32, device=dev); st = torch.zeros_like(it)
         err = torch.empty(B, dtype=torch.float64, device=dev)
+        if cov or point_cov:
+            used = torch.zeros_like(it)
+            res = dict(R_t=out.transpose(1, 2), Reconst=rec.transpose(1, 2), iter=it, repr_err=err, used=used, status=st)
+            if loss is not None:
+                res["weight"] = torch.empty((B, N, M), dtype=torch.float64, device=dev)
+            P = 6 * (M - 1)
+            res["cov"] = torch.empty((B, P, P), dtype=torch.float64, device=dev); res["sigma0"] = torch.empty(B, dtype=torch.float64, device=dev)
+            if point_cov:
+                res["point_cov"] = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+            _check(self.lib, self.lib.tff_bundle_adjust_tracks_cov_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N,
+                                                                             self._p(x0), self._p(out), self._p(rec), self._p(it), self._p(err), self._p(used),
+                                                                             self._p(st), LOSS_IDS[loss] if loss is not None else 0,
+                                                                             float(scale) if loss is not None else 0.0, self._p(res.get("weight")),
+                                                                             self._p(res["cov"]), self._p(res["sigma0"]), self._p(res.get("point_cov"))),
+                   "tff_bundle_adjust_tracks_cov_batch_dev")
+            return res
         if missing == "point" and loss is not None:
             used = torch.zeros_like(it)
             weight = torch.empty((B, N, M), dtype=torch.float64, device=dev)
@@ -1138,6 +1193,43 @@ class Context:
                                                                     self._p(x0), self._p(out), self._p(rec), self._p(it), self._p(err), self._p(st)),
                "tff_bundle_adjust_views_batch_dev")
         return dict(R_t=out.transpose(1, 2), Reconst=rec.transpose(1, 2), iter=it, repr_err=err, status=st)
+
+    def ba_tracks_covariance(self, calm, R_t, corresp, reconst, loss=None, scale=None, point_cov=False):
+        """The covariance of a bundle adjustment over tracks AT the given poses and points (tff_ba_tracks_covariance_batch_dev,
+        include/tftfund_tracks_cov.h; no iteration is run): calm (3M,3) or (B,3M,3); R_t (B,3M,4), first camera free, any common scale; corresp
+        (B,N,2M), non-finite = not seen; reconst (B,3,N) in the frame of R_t, as bundle_adjust_views(..., missing="point") takes and returns them; loss,
+        scale as there.  -> dict(cov (B,P,P), sigma0 (B,)[, point_cov (B,N,6)]), P = 6 (M - 1): cov is that of (angles of cameras 2..M, their
+        translations) -- the angles of R = Rx Ry Rz, see euler_cov_to_rotvec_views -- in the output frame, camera 1 = [I|0] and |t2| = 1; the rows and
+        columns of a camera nobody sees are 0; sigma0^2 = r'r / dof (normalised units without a loss, pixels with one).  NaN where there is no
+        redundancy, for non-finite poses or points, and where view 2 is not seen."""
+        _check_tracks_loss("point", loss, scale)                             # (before a device is touched)
+        cs = tuple(corresp.shape)
+        if len(cs) != 3 or cs[2] % 2 or not 2 <= cs[2] // 2 <= 6:
+            raise ValueError("corresp must be (B,N,2M) with M = 2 .. 6 views")
+        if tuple(R_t.shape) != (cs[0], 3 * cs[2] // 2, 4) or tuple(calm.shape) not in ((3 * cs[2] // 2, 3), (cs[0], 3 * cs[2] // 2, 3)):
+            raise ValueError("M views: corresp (B,N,2M), R_t (B,3M,4), calm (3M,3) or (B,3M,3)")
+        if reconst is None or tuple(reconst.shape) != (cs[0], 3, cs[1]):
+            raise ValueError("reconst must be (B,3,N)")
+        self._begin()
+        corresp = self._t(corresp); B, N, M2 = corresp.shape
+        M = M2 // 2
+        dev = corresp.device
+        calm = self._t(calm)
+        if calm.dim() == 2:
+            calm_cm, stride = calm.t().contiguous().reshape(9 * M), 0
+        else:
+            calm_cm, stride = calm.transpose(1, 2).contiguous().reshape(B * 9 * M), 9 * M
+        rt_cm = self._t(R_t).transpose(1, 2).contiguous()
+        x = self._t(reconst).transpose(1, 2).contiguous()
+        P = 6 * (M - 1)
+        out = dict(cov=torch.empty((B, P, P), dtype=torch.float64, device=dev), sigma0=torch.empty(B, dtype=torch.float64, device=dev))
+        if point_cov:
+            out["point_cov"] = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+        _check(self.lib, self.lib.tff_ba_tracks_covariance_batch_dev(self.handle, M, self._p(calm_cm), stride, self._p(rt_cm), self._p(corresp), B, N, self._p(x),
+                                                                     LOSS_IDS[loss] if loss is not None else 0, float(scale) if loss is not None else 0.0,
+                                                                     self._p(out["cov"]), self._p(out["sigma0"]), self._p(out.get("point_cov"))),
+               "tff_ba_tracks_covariance_batch_dev")
+        return out
 
     def pose_sampled(self, method, scene, calm, sample_idx):
         """Minimal-sample hypotheses (config 4): scene (Ns, 6), sample_idx (B, n) int32 -> R_t_2, R_t_3 (B,3,4), T, status."""

@@ -14,7 +14,8 @@ def _stale():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    deps += [os.path.join(HERE, "..", "include", h) for h in ("tftfund.h", "tftfund_adaptive.h", "tftfund_guided.h", "tftfund_loss.h", "tftfund_cov.h", "tftfund_tracks.h", "tftfund_tracks_loss.h")]
+    deps += [os.path.join(HERE, "..", "include", h) for h in ("tftfund.h", "tftfund_adaptive.h", "tftfund_guided.h", "tftfund_loss.h", "tftfund_cov.h", "tftfund_tracks.h", "tftfund_tracks_loss.h",
+                                                             "tftfund_tracks_cov.h")]
     return any(os.path.getmtime(p) > t for p in deps if os.path.isfile(p))
 
 

@@ -26,6 +26,7 @@
 #include "ba_cov_kernel.h"
 #include "ba_tracks_kernel.h"
 #include "ba_tracks_loss_kernel.h"
+#include "ba_tracks_cov_kernel.h"
 
 namespace {
 
@@ -87,6 +88,7 @@ struct tff_ctx {
     DevBuf ba_plan, ba_pack, ba_host;      // tff_bundle_adjust_ragged_*: the plan (O(B)), the compact copies of a masked call (100 bytes x n_total), mask + used of a _host call
     DevBuf cov_plan, cov_pack, cov_rec, cov_io;   // tff_ba_covariance_* / tff_bundle_adjust_cov_*: the plan (O(B)), the compact copies of a masked call (124 bytes x n_total), the points of a call without `reconst`, the staging of a _host call
     DevBuf tracks_used;                    // tff_bundle_adjust_tracks_batch_host: the staged `used` (4 B bytes)
+    DevBuf tracks_cov_x, tracks_cov_rec, tracks_cov_io;   // tff_ba_tracks_covariance_* / tff_bundle_adjust_tracks_cov_*: the points in the frame of camera 1 (24 B N bytes), the points of a call without `reconst`, the staging of a _host call
     DevBuf tracks_weight, tracks_status;   // tff_bundle_adjust_tracks_loss_batch_*: the staged weights of a _host call (8 B N M bytes); the statuses of a TFF_LOSS_NONE call with weights and no status output (4 B bytes)
     int kernel_variant = 0;                // TFF_OPT_KERNEL
     int gh_exact = 0;                      // TFF_OPT_GH_EXACT
@@ -1069,7 +1071,7 @@ int launch_robust_scenes(tff_ctx* c, const RaggedRoute& route, const ScenesCall&
 
 extern "C" {
 
-int tff_version(void) { return 109; }
+int tff_version(void) { return 110; }
 const char* tff_last_error(void) { return g_err.c_str(); }
 
 int tff_ctx_create(tff_ctx** out, int device) {
@@ -1095,7 +1097,7 @@ void tff_ctx_destroy(tff_ctx* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->handover) (void)hipEventDestroy(c->handover);
     for (DevBuf* b : {&c->in, &c->calm, &c->out, &c->idx, &c->scratch_status, &c->gh_rec, &c->gh_topt, &c->gh_init, &c->spill, &c->pre_rec, &c->retry, &c->ragged, &c->ragged_off, &c->robust_hyp, &c->robust_counts,
-                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io, &c->tracks_used, &c->tracks_weight, &c->tracks_status})
+                      &c->robust_cand, &c->guided_ends, &c->guided_order, &c->ba_plan, &c->ba_pack, &c->ba_host, &c->ba_weight, &c->cov_plan, &c->cov_pack, &c->cov_rec, &c->cov_io, &c->tracks_used, &c->tracks_weight, &c->tracks_status, &c->tracks_cov_x, &c->tracks_cov_rec, &c->tracks_cov_io})
         b->release();
     delete c;
 }
@@ -1725,6 +1727,29 @@ int launch_bundle_adjust_tracks_loss(tff_ctx* c, int32_t M, tff::BatArgs a, int3
         default: return launch_bundle_adjust_tracks_loss<6>(c, loss, la);
     }
 }
+// ... and its covariance at given poses and points (csrc/ba_tracks_cov_kernel.h, include/tftfund_tracks_cov.h): fifteen instances, M x loss; the LDS does not
+// grow with N, so there are no launch classes
+static_assert(tff::batc_lds_bytes<tff::BAV_MAX_VIEWS>() <= 64 * 1024, "k_ba_tracks_cov's LDS does not grow with N");
+template <int M>
+int launch_ba_tracks_cov(tff_ctx* c, int32_t loss, const tff::BatCovArgs& a) {
+    const unsigned grid = tff::pose_grid(a.B);
+    constexpr size_t lds = tff::batc_lds_bytes<M>();
+    if (loss == TFF_LOSS_NONE) return launch(c, tff::k_ba_tracks_cov<M, tff::BA_LOSS_NONE>, grid, 64, lds, a);
+    return loss == TFF_LOSS_HUBER ? launch(c, tff::k_ba_tracks_cov<M, tff::BA_LOSS_HUBER>, grid, 64, lds, a)
+                                  : launch(c, tff::k_ba_tracks_cov<M, tff::BA_LOSS_CAUCHY>, grid, 64, lds, a);
+}
+int launch_ba_tracks_cov(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt, const double* corresp, int64_t B, int32_t N,
+                         const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    TFF_TRY(c->tracks_cov_x.reserve((size_t)B * 3 * (size_t)N * sizeof(double) + 8));
+    const tff::BatCovArgs a{calm, (long)calm_stride, Rt, corresp, (long)B, N, reconst, scale, (double*)c->tracks_cov_x.p, cov, sigma0, point_cov};
+    switch (M) {
+        case 2: return launch_ba_tracks_cov<2>(c, loss, a);
+        case 3: return launch_ba_tracks_cov<3>(c, loss, a);
+        case 4: return launch_ba_tracks_cov<4>(c, loss, a);
+        case 5: return launch_ba_tracks_cov<5>(c, loss, a);
+        default: return launch_ba_tracks_cov<6>(c, loss, a);
+    }
+}
 int check_views(int32_t M, const void* calm, int64_t calm_stride, const void* Rt_in, const void* corresp, int64_t B, int32_t N, const void* Rt) {
     if (M < tff::BAV_MIN_VIEWS || M > tff::BAV_MAX_VIEWS) return fail(TFF_E_INVALID, "bundle adjustment takes 2 .. 6 views");
     if (B < 0 || N < 0) return fail(TFF_E_INVALID, "negative batch or correspondence count");
@@ -2172,6 +2197,82 @@ int tff_bundle_adjust_tracks_loss_batch_host(tff_ctx* c, int32_t M, const double
         if (weight) TFF_HIP(hipMemcpyAsync(weight, d_w, nw, hipMemcpyDeviceToHost, c->stream));
         return ba_stage_out(c, (size_t)B, npt, s, reconst, iter, repr_err, status);
     });
+}
+
+// ... and the covariance of its poses and points (launch_ba_tracks_cov above; include/tftfund_tracks_cov.h)
+int tff_ba_tracks_covariance_batch_dev(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt, const double* corresp, int64_t B,
+                                       int32_t N, const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt, corresp, B, N, cov));
+    TFF_TRY(check_ba_cov(reconst, cov, sigma0, B));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        return launch_ba_tracks_cov(c, M, calm, calm_stride, Rt, corresp, B, N, reconst, loss, scale, cov, sigma0, point_cov);
+    });
+}
+int tff_ba_tracks_covariance_batch_host(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt, const double* corresp, int64_t B,
+                                        int32_t N, const double* reconst, int32_t loss, double scale, double* cov, double* sigma0, double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt, corresp, B, N, cov));
+    TFF_TRY(check_ba_cov(reconst, cov, sigma0, B));
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        const size_t nb = (size_t)B, nn = nb * (size_t)N, ncal = (calm_stride ? nb : 1) * 9 * (size_t)M, pp = (size_t)(36 * (M - 1) * (M - 1));
+        // corresp (2M) | reconst (3) | point_cov (6) per point, Rt | cov | sigma0 per item, calm
+        TFF_TRY(c->tracks_cov_io.reserve(((2 * (size_t)M + 9) * nn + (12 * (size_t)M + pp + 1) * nb + ncal) * sizeof(double)));
+        double* d_in = (double*)c->tracks_cov_io.p;
+        double* d_x = d_in + 2 * (size_t)M * nn;
+        double* d_pc = d_x + 3 * nn;
+        double* d_rt = d_pc + 6 * nn;
+        double* d_cov = d_rt + 12 * (size_t)M * nb;
+        double* d_s0 = d_cov + pp * nb;
+        double* d_cal = d_s0 + nb;
+        TFF_HIP(hipMemcpyAsync(d_in, corresp, 2 * (size_t)M * nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_x, reconst, 3 * nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_rt, Rt, 12 * (size_t)M * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_HIP(hipMemcpyAsync(d_cal, calm, ncal * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        TFF_TRY(launch_ba_tracks_cov(c, M, d_cal, calm_stride, d_rt, d_in, B, N, d_x, loss, scale, d_cov, d_s0, point_cov ? d_pc : nullptr));
+        TFF_HIP(hipMemcpyAsync(cov, d_cov, pp * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipMemcpyAsync(sigma0, d_s0, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (point_cov) TFF_HIP(hipMemcpyAsync(point_cov, d_pc, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        TFF_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+// the adjustment followed by the covariance at its outputs, on one stream
+int tff_bundle_adjust_tracks_cov_batch_dev(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                           int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                           int32_t* used, int32_t* status, int32_t loss, double scale, double* weight, double* cov, double* sigma0,
+                                           double* point_cov) {
+    TFF_ENTER(c);
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    return run_batch(c, B, true, nullptr, nullptr, [&] {
+        double* rec = reconst;
+        if (!rec) {
+            TFF_TRY(c->tracks_cov_rec.reserve((size_t)B * 3 * (size_t)N * sizeof(double) + 8));
+            rec = (double*)c->tracks_cov_rec.p;
+        }
+        TFF_TRY(launch_bundle_adjust_tracks_loss(c, M, tff::BatArgs{tff::BavArgs{calm, (long)calm_stride, Rt_in, corresp, (long)B, N, reconst0, Rt, rec, iter,
+                                                                                 repr_err, status}, used}, loss, scale, weight));
+        return launch_ba_tracks_cov(c, M, calm, calm_stride, Rt, corresp, B, N, rec, loss, scale, cov, sigma0, point_cov);
+    });
+}
+// host-pointer form: the two host calls one after the other (each stages, runs and synchronises), the points in between kept by the caller or here
+int tff_bundle_adjust_tracks_cov_batch_host(tff_ctx* c, int32_t M, const double* calm, int64_t calm_stride, const double* Rt_in, const double* corresp,
+                                            int64_t B, int32_t N, const double* reconst0, double* Rt, double* reconst, int32_t* iter, double* repr_err,
+                                            int32_t* used, int32_t* status, int32_t loss, double scale, double* weight, double* cov, double* sigma0,
+                                            double* point_cov) {
+    if (!c) return fail(TFF_E_INVALID, "null context");
+    TFF_TRY(check_loss(loss, scale));
+    TFF_TRY(check_views(M, calm, calm_stride, Rt_in, corresp, B, N, Rt));
+    if (B > 0 && (!cov || !sigma0)) return fail(TFF_E_INVALID, "the covariance needs cov and sigma0");
+    std::vector<double> own;
+    double* rec = reconst;
+    if (!rec && B > 0 && N > 0) { own.resize((size_t)B * 3 * (size_t)N); rec = own.data(); }
+    TFF_TRY(tff_bundle_adjust_tracks_loss_batch_host(c, M, calm, calm_stride, Rt_in, corresp, B, N, reconst0, Rt, rec, iter, repr_err, used, status, loss, scale, weight));
+    return tff_ba_tracks_covariance_batch_host(c, M, calm, calm_stride, Rt, corresp, B, N, rec, loss, scale, cov, sigma0, point_cov);
 }
 
 // linearF (refine = 0) / optimF (refine = 1) for the view pairs (1,2) and (1,3)
